@@ -12,6 +12,11 @@ Multi-GPU: replicas only - each rank samples its own (prompt, reference-video) p
 one RCCL broadcast of the packed fp16 weights from rank 0 before the timed region.
 
   python bench.py --gpus N --steps K --warmup W      (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds everything else: the eager /
+roofline-probe videos, the three-lanes x one-video regime, the VAE calls, the stock-PyTorch GPU and CPU baselines, the
+roofline / HBM-traffic tables and the detail record (profiles/bench_detail.json).  `--dump-outputs DIR` writes the final
+latents of the last timed round as DIR/latents.npy (float32), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -399,17 +404,33 @@ def compact_line(res, detail_path, limit=4000):
     return out
 
 
+DETAIL_FILE = os.path.join("profiles", "bench_detail.json")
+DUMP_MAX_BYTES = 64 << 20
+
+
 def write_detail(res):
-    """full record -> profiles/r06_bench_detail.json (and gpurun_out/, which is what travels back from a GPU box)"""
-    rel = os.path.join("profiles", "r06_bench_detail.json")
-    for d in ("profiles", "gpurun_out"):
-        try:
-            os.makedirs(os.path.join(ROOT, d), exist_ok=True)
-            with open(os.path.join(ROOT, d, "r06_bench_detail.json"), "w") as f:
-                json.dump(res, f, indent=1)
-        except OSError:
-            pass
-    return rel
+    """full record (--full) -> profiles/bench_detail.json (not tracked: the committed r0N_bench_detail.json are the rounds' records)"""
+    try:
+        os.makedirs(os.path.join(ROOT, os.path.dirname(DETAIL_FILE)), exist_ok=True)
+        with open(os.path.join(ROOT, DETAIL_FILE), "w") as f:
+            json.dump(res, f, indent=1)
+    except OSError:
+        pass
+    return DETAIL_FILE
+
+
+def dump_outputs(outdir, latents, name="latents"):
+    """--dump-outputs: the final latents of the last timed round (every lane's videos, lane order) as float32 .npy.  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of the flattened array is written instead (values + their flat indices)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    a = latents.float().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // 16           # float32 values + int64 indices
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+        np.save(os.path.join(outdir, name + "_sample_index.npy"), idx)
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def main():
@@ -426,7 +447,7 @@ def main():
     ap.add_argument("--sparsectrl", action="store_true", help="BASELINE config 4: add the SparseCtrl (i2v_rgb) encoder pass")
     ap.add_argument("--no-graphs", action="store_true", help="time the eager launch sequence instead of the per-step hipGraphs")
     ap.add_argument("--gemm-lanes", type=int, default=0, help="value handed to ops.set_gemm_share (0 = the number of videos in flight)")
-    ap.add_argument("--shapes-out", default=None, help="write the per-(kernel, shape) GEMM time table of the probe video to this JSON file")
+    ap.add_argument("--shapes-out", default=None, help="(--full) write the per-(kernel, shape) GEMM time table of the probe video to this JSON file")
     ap.add_argument("--no-gn-epilogue", action="store_true", help="A/B: GroupNorm statistics always from their own pass over the tensor "
                     "(round 5) instead of the producing GEMM's epilogue (mc_gemm_gnstats_f16)")
     ap.add_argument("--no-norm-fusion", action="store_true", help="A/B: LayerNorm / GroupNorm as separate launches in front of the "
@@ -439,7 +460,7 @@ def main():
                     "runs that should hold the timed regime's kernels only: tools/gpu_profile_r05.sh)")
     ap.add_argument("--probe-one-lane", action="store_true", help="roofline probe video with the tile choice of ONE video in flight "
                     "(round 4's probe regime) instead of the timed region's")
-    ap.add_argument("--no-detail", action="store_true", help="do not write profiles/r06_bench_detail.json")
+    ap.add_argument("--no-detail", action="store_true", help="(--full) do not write profiles/bench_detail.json")
     ap.add_argument("--no-vae", action="store_true", help="skip the (untimed, informational) VAE decode / encode measurement")
     ap.add_argument("--batch", type=int, default=0, help="(0 = automatic, see auto_packing) videos batched into ONE launch sequence per lane (latents [V, ...], text "
                     "[u_1 .. u_V | c_1 .. c_V]: the same kernels on V times the rows); --inflight lanes x --batch videos are in "
@@ -453,6 +474,11 @@ def main():
                     "results bit-identical to the one-at-a-time run (checked in the run: `eager.identical_to_graph_path`, "
                     "tools/concurrency_check.py).  --steps videos are processed in rounds of up to this many, never leaving "
                     "a single video for the last round when it can be avoided (4 -> 2 + 2, 5 -> 3 + 2, 7 -> 3 + 2 + 2)")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: probe / eager videos and roofline tables, the "
+                    "three-lanes x one-video regime, VAE calls, stock-PyTorch GPU and CPU baselines, detail record (the --no-* "
+                    "switches above trim these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the final latents of the last timed round to "
+                    "DIR/latents.npy (float32; with --gpus N each rank writes DIR/latents_rank<r>.npy)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -518,7 +544,7 @@ def main():
     # The timed path replays one hipGraph per DDIM step (sampler.enable_graphs: bit-identical to the eager launches,
     # tests/test_fullsize_properties.py); everything that differs between videos enters through static buffers.  The
     # motion-representation extraction (once per video) stays eager.  `--no-graphs` times the eager launch sequence instead.
-    probe = LaunchProbe().install()
+    probe = LaunchProbe().install() if args.full else None
     use_graphs = not args.no_graphs
     # Independent (prompt, reference-video) samples are the unit of parallelism of this workload.  `--inflight`
     # of them can run concurrently inside one GPU, each on its own HIP stream with its own sampler (and graphs): the launch
@@ -564,10 +590,9 @@ def main():
                 step_events.append((i < G_STEPS, pending.pop(k), ev))
 
         for k_act in plan_rounds(nvideos // VB, NF):
-            xs = sample_interleaved(smps[:k_act], lane_inputs[:k_act], streams[:k_act], add_noise_step=400, ctrl=ctrl,
-                                    on_step=on_step)
-            last = xs[0]
-        return last
+            last = sample_interleaved(smps[:k_act], lane_inputs[:k_act], streams[:k_act], add_noise_step=400, ctrl=ctrl,
+                                      on_step=on_step)
+        return last      # the last round's final latents, one [VB, 4, F, h, w] tensor per lane
 
     warm_videos = max(NF * VB, (args.warmup + VB - 1) // VB * VB)     # every lane's first pass captures its graphs / fills its allocator pool: never timed
     t_warm0 = time.perf_counter()
@@ -583,7 +608,7 @@ def main():
     torch.cuda.synchronize()
     step_events = []
     t0 = time.perf_counter()
-    out = run_videos(args.steps, step_events)
+    outs = run_videos(args.steps, step_events)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -591,7 +616,11 @@ def main():
     elapsed = time.perf_counter() - t0
     timed_reserved = torch.cuda.max_memory_reserved(dev) / 2 ** 30
     timed_allocated = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    out = outs[0]
     assert torch.isfinite(out.float()).all(), "non-finite latents"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch.cat([x.detach().cpu() for x in outs], 0),
+                     "latents" if world == 1 else "latents_rank%d" % rank)
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -602,7 +631,7 @@ def main():
     # inside a graph replay.  `eager` also reports what the un-graphed loop costs on this box.
     eager_info = None
     probe_elapsed = None
-    if rank == 0 and not args.no_probe:
+    if rank == 0 and args.full and not args.no_probe:
         sme = MotionCloneSampler(eng, cfg_scale=7.5, motion_guidance_weight=2000.0, warm_up_steps=10, cool_up_steps=10,
                                  num_inference_steps=N_STEPS, guidance_steps=G_STEPS, guidance_scale=G_SCALE, controlnet=ceng,
                                  batch_guided=not args.two_b1_guided)
@@ -640,7 +669,7 @@ def main():
     # (motionclone_amd.launch --lanes 3) gives the unmodified entry scripts, whose calls carry one example each.  Six videos
     # after their own warm-up round, outside the timed region.
     lanes_only = None
-    if rank == 0 and world == 1 and not args.no_probe and use_graphs and VB > 1 and not args.sparsectrl:
+    if rank == 0 and world == 1 and args.full and not args.no_probe and use_graphs and VB > 1 and not args.sparsectrl:
         try:
             torch.cuda.empty_cache()       # what the eager / probe passes left cached (~60 GiB at 5 batched videos)
             ops.set_gemm_share(3)
@@ -666,7 +695,7 @@ def main():
                       note="one graph per DDIM step, captured during warm-up; latents / text / representation refreshed by "
                            "device copies into static buffers before each replay; extraction eager")
     vae_info = None
-    if rank == 0 and world == 1 and not args.no_vae:
+    if rank == 0 and world == 1 and args.full and not args.no_vae:
         vae_info = vae_extras(dev, out, args.frames, args.size)
     if rank == 0:
         gsec = [e0.elapsed_time(e1) / 1e3 for g, e0, e1 in step_events if g]
@@ -678,14 +707,14 @@ def main():
         tflop_video = G_STEPS * tg + (N_STEPS - G_STEPS) * tp + te
         roof_all = probe.summary(probe_elapsed) if probe_elapsed else {}
         by_shape = probe.by_shape() if probe_elapsed else []
-        if args.shapes_out:
+        if args.shapes_out and probe_elapsed:
             json.dump(by_shape, open(args.shapes_out, "w"), indent=1)
         # HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md), per SHAPE, next to
         # that shape's algorithmic bytes; a family's `traffic` is the launch-weighted mean over its measured shapes and
         # `traffic_vs_algorithmic` the ratio on exactly those shapes
         traffic_rows = []
         tfile = os.path.join(ROOT, "profiles", "hbm_traffic_per_shape.json")
-        if os.path.exists(tfile) and (args.frames, args.size) == (16, 512):
+        if args.full and os.path.exists(tfile) and (args.frames, args.size) == (16, 512):
             pmc = json.load(open(tfile))
             for row in by_shape:
                 for m in pmc:
@@ -708,7 +737,7 @@ def main():
                 "one video in flight" if args.probe_one_lane else "the timed region (%d in flight)" % NF))
         roof_timed = None
         tdf = os.path.join(ROOT, TIMED_DURATIONS_FILE)
-        if (os.path.exists(tdf) and (args.frames, args.size, N_STEPS, G_STEPS) == (16, 512, 30, 18) and use_graphs
+        if (args.full and os.path.exists(tdf) and (args.frames, args.size, N_STEPS, G_STEPS) == (16, 512, 30, 18) and use_graphs
                 and not args.sparsectrl and not args.probe_one_lane):
             try:
                 roof_timed = timed_roofline(roof_all, json.load(open(tdf)), NF, VB)
@@ -760,7 +789,7 @@ def main():
             "eager": eager_info,
             "three_lanes_x_one_video": lanes_only,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del eng, smp, smps
             torch.cuda.empty_cache()
             # the two baseline legs run after the measurement; a failure in one of them must not lose the bench line
@@ -779,7 +808,7 @@ def main():
             # result (measured above, one video at a time, nothing overlapped): the conservative end-to-end figure
             per_video = elapsed / args.steps + vae_info["decode_sec_per_video"] + vae_info["encode_sec_per_video"]
             res["videos_per_min_incl_vae"] = world * 60.0 / per_video
-        detail = write_detail(res) if not args.no_detail else None
+        detail = write_detail(res) if args.full and not args.no_detail else None
         sys.stdout.flush()
         print(compact_line(res, detail), flush=True)
     if dist is not None:

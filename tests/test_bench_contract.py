@@ -213,3 +213,21 @@ def test_automatic_packing_divides_the_timed_videos(bench):
     for k in range(1, 41):
         nf, vb = bench.auto_packing(k, 16, 512, False)
         assert vb == 1 or k % (nf * vb) == 0
+
+
+def test_dump_outputs_writes_the_latents_as_float32(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the last timed round's latents as DIR/latents.npy in float32; above the size cap a fixed, seeded
+    sample of the flattened array (values + flat indices), the same from run to run"""
+    import numpy as np
+    import torch
+    x = torch.randn(2, 4, 3, 8, 8, generator=torch.Generator().manual_seed(0)).half()
+    bench.dump_outputs(str(tmp_path / "full"), x)
+    a = np.load(tmp_path / "full" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == tuple(x.shape) and np.array_equal(a, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), x, "lat")
+    v, i = np.load(tmp_path / "s1" / "lat.npy"), np.load(tmp_path / "s1" / "lat_sample_index.npy")
+    assert v.dtype == np.float32 and v.nbytes + i.nbytes <= 4096 and len(np.unique(i)) == len(i) == 256
+    assert np.array_equal(v, x.float().numpy().reshape(-1)[i])
+    assert np.array_equal(i, np.load(tmp_path / "s2" / "lat_sample_index.npy"))

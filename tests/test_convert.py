@@ -1,7 +1,6 @@
 """Checkpoint conversion / LoRA merge: motionclone_amd.utils.convert against the reference's
-own converters (loaded by file path from /root/reference, skipped where the tree is absent) and against an inverse
+own converters (their results recorded in tests/golden/reference_records.pt) and against an inverse
 mapping written independently here (round trip - this half also runs on the GPU box)."""
-import importlib.util
 import os
 import re
 import types
@@ -10,21 +9,13 @@ import pytest
 import torch
 
 from motionclone_amd.utils import convert as C
-from oracle import reference_shim as shim
 from oracle import unet3d_ref as U
 from oracle import vae_ref as V
 
 
-def _ref(name):
-    shim.install()
-    path = os.path.join(shim.REFERENCE_ROOT, "motionclone", "utils", name + ".py")
-    spec = importlib.util.spec_from_file_location("_ref_" + name, path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-needs_ref = pytest.mark.skipif(not shim.available(), reason="reference tree not present")
+def _rec():
+    """what the reference computed (tests/golden/make_reference_records.py)"""
+    return torch.load(os.path.join(os.path.dirname(__file__), "golden", "reference_records.pt"), weights_only=False)
 
 
 # ---- independent inverse maps: diffusers layout -> LDM layout --------------------------------------------
@@ -140,20 +131,29 @@ def test_vae_round_trip():
         _same(C.convert_ldm_vae_checkpoint(vae_to_ldm(sd, len(cfg["block_out_channels"]))), sd)
 
 
-@needs_ref
+def _same_as_recorded(out, inp, rec):
+    """`rec`: the reference converter's output on `inp` as {key: (input key, shape)} for a view of one input tensor, else
+    {key: tensor} (tests/golden/make_reference_records.py)"""
+    assert set(out) == set(rec), (sorted(set(out) - set(rec))[:5], sorted(set(rec) - set(out))[:5])
+    for k, r in rec.items():
+        want = inp[r[0]].reshape(r[1]) if isinstance(r, tuple) else r
+        assert out[k].shape == want.shape and torch.equal(out[k], want), k
+
+
 def test_converters_match_reference(unet_sd):
-    R = _ref("convert_from_ckpt")
+    rec = _rec()["convert"]
     ldm = unet_to_ldm(unet_sd)
     cfg = dict(layers_per_block=2, class_embed_type=None)
-    _same(C.convert_ldm_unet_checkpoint(dict(ldm), cfg), R.convert_ldm_unet_checkpoint(dict(ldm), cfg))
+    _same_as_recorded(C.convert_ldm_unet_checkpoint(dict(ldm), cfg), ldm, rec["unet"])
     vcfg = V.SD15_VAE_CONFIG
     vsd = {k: torch.randn(s) if len(s) < 3 else torch.zeros(s) for k, s in V.param_shapes(vcfg).items()}
     vldm = vae_to_ldm(vsd, 4)
+    assert sorted(k for k, v in vldm.items() if not v.any()) == rec["vae_ldm_zero_keys"]
     ref_cfg = dict(down_block_types=["DownEncoderBlock2D"] * 4, up_block_types=["UpDecoderBlock2D"] * 4)
-    _same(C.convert_ldm_vae_checkpoint(dict(vldm), ref_cfg), R.convert_ldm_vae_checkpoint(dict(vldm), ref_cfg))
+    _same_as_recorded(C.convert_ldm_vae_checkpoint(dict(vldm), ref_cfg), vldm, rec["vae"])
     clip = {"cond_stage_model.transformer.text_model.embeddings.token_embedding.weight": torch.ones(3, 2),
             "model.diffusion_model.out.2.bias": torch.zeros(4)}
-    _same(C.convert_ldm_clip_checkpoint_concise(clip), R.convert_ldm_clip_checkpoint_concise(clip))
+    _same(C.convert_ldm_clip_checkpoint_concise(clip), rec["clip"])
 
 
 class _Lin(torch.nn.Module):
@@ -201,19 +201,18 @@ def test_lora_merge_math():
         C.convert_lora(pipe, {"lora_unet_nope.lora_down.weight": torch.zeros(1, 1), "lora_unet_nope.lora_up.weight": torch.zeros(1, 1)})
 
 
-@needs_ref
 def test_lora_merge_matches_reference():
-    R = _ref("convert_lora_safetensor_to_diffusers")
+    rec = _rec()["convert"]["lora"]     # the reference's convert_lora(alpha 0.8) + load_diffusers_lora(alpha 1.0) on the toy UNet
     kohya, diff = _lora_sd(1)
-    a, b = _toy_unet(), _toy_unet()
-    b.load_state_dict(a.state_dict())
-    pa, pb = types.SimpleNamespace(unet=a, text_encoder=None), types.SimpleNamespace(unet=b, text_encoder=None)
+    a = _toy_unet()
+    a.load_state_dict(rec["before"])
+    pa = types.SimpleNamespace(unet=a, text_encoder=None)
     C.convert_lora(pa, kohya, alpha=0.8)
-    R.convert_lora(pb, kohya, alpha=0.8)
     C.load_diffusers_lora(pa, diff, alpha=1.0)
-    R.load_diffusers_lora(pb, diff, alpha=1.0)
-    for (k, x), (_, y) in zip(a.state_dict().items(), b.state_dict().items()):
-        assert torch.allclose(x, y, atol=1e-6), k
+    assert list(a.state_dict()) == list(rec["after"])
+    for k, x in a.state_dict().items():
+        assert torch.allclose(x, rec["after"][k], atol=1e-6), k
+        assert not torch.equal(x, rec["before"][k]), k
 
 
 def test_load_weights_end_to_end(tmp_path):

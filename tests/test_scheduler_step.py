@@ -1,7 +1,8 @@
 """schedule_customized_step (motionclone_functions.py:285-409) with every branch, through mc_ddim_step_general_f16:
-the oracle restatement is pinned to the reference's own function where the reference tree exists (CPU container), and
+the oracle restatement is pinned to the reference's own function (its results recorded in tests/golden/reference_ddim_*.pt), and
 the kernel path is compared with the oracle on the host simulator and on the GPU."""
 import itertools
+import os
 import types
 
 import pytest
@@ -47,37 +48,38 @@ def _rel(a, b):
     return ((a.float().cpu() - b).norm() / b.norm().clamp_min(1e-20)).item()
 
 
-@pytest.mark.skipif(not shim.available(), reason="reference tree not present")
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c.values()))
+def case_id(case):
+    return "-".join(str(v) for v in case.values())
+
+
+def _records(prediction_type):
+    """the reference's own schedule_customized_step on these inputs, recorded by tests/golden/make_reference_records.py"""
+    return torch.load(os.path.join(os.path.dirname(__file__), "golden", "reference_ddim_%s.pt" % prediction_type), weights_only=False)
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_oracle_restatement_matches_the_reference_function(case):
-    shim.install()
-    import motionclone.utils.motionclone_functions as ref      # the reference's module (shim.install put it first on sys.path)
-    assert ref.__file__.startswith(shim.REFERENCE_ROOT)
+    rec = _records(case["prediction_type"])[case_id(case)]
     sample, mo, score, noise = _tensors()
     sch = shim.DDIMScheduler(beta_start=0.00085, beta_end=0.012, steps_offset=1, clip_sample=case["clip_sample"],
                              prediction_type=case["prediction_type"])
-    sch.variance_type = "fixed_small"
-    sch.customized_step = ref.schedule_customized_step.__get__(sch)
-    sch.customized_set_timesteps = ref.schedule_set_timesteps.__get__(sch)
-    sch.customized_set_timesteps(6, 3, 0.4, device="cpu", timestep_spacing_type="uneven")
+    assert torch.equal(sch.alphas_cumprod, rec["alphas_cumprod"]) and torch.equal(sch.final_alpha_cumprod, rec["final_alpha_cumprod"])
+    sch.timesteps = rec["timesteps"]     # the reference's schedule_set_timesteps(6, 3, 0.4, uneven)
     for step_index in (0, 5):
-        kw = dict(eta=case["eta"], use_clipped_model_output=case["use_clipped_model_output"],
-                  variance_noise=noise if case["eta"] > 0 else None)
-        got = sch.customized_step(mo.clone(), step_index, sample, score=score, guidance_scale=0.6, **kw)
+        got = rec["steps"][step_index]
         want = _oracle(case, step_index, sample, mo, score, noise, sch, guidance_scale=0.6)
-        for a, b in zip(got[:2], want[:2]):
+        for a, b in zip(got["full"][:2], want[:2]):
             assert torch.allclose(a, b, rtol=1e-5, atol=1e-5)
-        assert abs(float(got[2]) - float(want[2])) < 1e-7
+        assert abs(got["full"][2] - float(want[2])) < 1e-7
         # score on a batch subset, and the early return
-        got = sch.customized_step(mo.clone(), step_index, sample, score=score[1:2], guidance_scale=0.6, indices=[1], **kw)
         want = _oracle(dict(case), step_index, sample, mo, score[1:2], noise, sch, guidance_scale=0.6, indices=[1])
-        assert torch.allclose(got[0], want[0], rtol=1e-5, atol=1e-5)
-        got = sch.customized_step(mo.clone(), step_index, sample, score=score, return_middle=True, **kw)
+        assert torch.allclose(got["subset"], want[0], rtol=1e-5, atol=1e-5)
         want = _oracle(case, step_index, sample, mo, score, noise, sch, return_middle=True)
-        assert torch.allclose(got[0], want[0], rtol=1e-5, atol=1e-5) and torch.allclose(got[3], want[3], rtol=1e-5, atol=1e-5)
+        assert torch.allclose(got["middle"][0], want[0], rtol=1e-5, atol=1e-5)
+        assert torch.allclose(got["middle"][1], want[3], rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c.values()))
+@pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_kernel_path_matches_oracle(backend, case):
     dev = backend
     sample, mo, score, noise = _tensors()
