@@ -268,6 +268,14 @@ int mc_cfg_ddim_step_f16(const void* eps_c, const void* eps_u, int ld, const voi
                          void* out, void* eps_out, float cfg, float sqrt_a_t, float sqrt_1m_a_t,
                          float sqrt_a_prev, float sqrt_1m_a_prev, float score_coef, int CL, int F, int HW,
                          void* stream);
+/* The same update for V videos in ONE launch (several videos packed into one launch sequence): eps_c / eps_u
+ * [(v f h w), ld] video-major, x, score (fp32, may be NULL), out, eps_out (may be NULL): [V, CL, F, H, W].  Same
+ * coefficients, same per-element arithmetic and order: every video's output is bit-identical to mc_cfg_ddim_step_f16 on
+ * that video's rows.  64-bit offsets; CL == 4 with 8-byte aligned rows reads a token's channels as one vector. */
+int mc_cfg_ddim_step_batched_f16(const void* eps_c, const void* eps_u, int ld, const void* x, const float* score,
+                                 void* out, void* eps_out, float cfg, float sqrt_a_t, float sqrt_1m_a_t,
+                                 float sqrt_a_prev, float sqrt_1m_a_prev, float score_coef, int V, int CL, int F, int HW,
+                                 void* stream);
 /* schedule_customized_step with every branch (motionclone_functions.py:285-409): prediction_type epsilon / sample /
  * v_prediction, clip_sample, use_clipped_model_output, eta > 0 with variance noise, the score term, return_middle.
  *   x0  = x0_s * sample + x0_m * model_output, clamped to [-clip, clip] if clip > 0;

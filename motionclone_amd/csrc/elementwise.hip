@@ -364,6 +364,54 @@ __global__ void cfg_ddim_kernel(const half_t* eps_c, const half_t* eps_u, int ld
     }
 }
 
+// cfg_ddim_kernel for V videos in ONE launch: eps_c / eps_u [(v f h w), ld] video-major (the token rows of a packed
+// forward); x, score, out, eps_out [V, CL, F, HW].  One thread per token: with VEC4 (CL == 4, rows and pointers 8-byte
+// aligned) the four channels of a token are one 8-byte load per operand, and the CL planes are written with the threads
+// running along the pixels.  Per element the expressions are cfg_ddim_kernel's, in its order: every video's output is
+// bit-identical to a one-video launch on that video's rows.  Token and element offsets are 64-bit (V * CL * F * HW and
+// the row offset tok * ld pass 2^31 at a few dozen full-size videos).
+__device__ __forceinline__ void cfg_ddim_elem(float ec, float eu, const half_t* x, const float* score, half_t* out,
+                                              half_t* eps_out, size_t idx, const DdimCoef& k) {
+    float eps = ec + k.cfg * (ec - eu);
+    float xv = (float)x[idx];
+    float x0 = (xv - k.sqrt_1m_a_t * eps) / k.sqrt_a_t;     // uses the un-guided eps (quirk A12)
+    float e2 = eps;
+    if (score) e2 -= k.score_coef * score[idx];
+    out[idx] = to_half(k.sqrt_a_prev * x0 + k.sqrt_1m_a_prev * e2);
+    if (eps_out) eps_out[idx] = to_half(eps);
+}
+
+// element offset of (v, c = 0, f, p) in [V, CL, F, HW] for token tok = (v F + f) HW + p (host-testable index arithmetic)
+__host__ __device__ inline size_t cfg_ddim_batched_dst(long tok, int CL, int F, int HW) {
+    const long p = tok % HW;
+    const long r = tok / HW;
+    const long f = r % F;
+    const long v = r / F;
+    return (((size_t)v * CL) * F + (size_t)f) * HW + (size_t)p;
+}
+
+template <bool VEC4>
+__global__ void cfg_ddim_batched_kernel(const half_t* eps_c, const half_t* eps_u, int ld, const half_t* x,
+                                        const float* score, half_t* out, half_t* eps_out, DdimCoef k, int V, int CL,
+                                        int F, int HW) {
+    const long tokens = (long)V * F * HW;
+    const size_t plane = (size_t)F * HW;
+    for (long tok = (long)blockIdx.x * blockDim.x + threadIdx.x; tok < tokens;
+         tok += (long)gridDim.x * blockDim.x) {
+        const size_t src = (size_t)tok * ld;
+        const size_t dst = cfg_ddim_batched_dst(tok, CL, F, HW);
+        if (VEC4) {
+            const half4_t c4 = ld4(eps_c + src), u4 = ld4(eps_u + src);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                cfg_ddim_elem((float)c4[c], (float)u4[c], x, score, out, eps_out, dst + c * plane, k);
+        } else {
+            for (int c = 0; c < CL; ++c)
+                cfg_ddim_elem((float)eps_c[src + c], (float)eps_u[src + c], x, score, out, eps_out, dst + c * plane, k);
+        }
+    }
+}
+
 // schedule_customized_step in full (motionclone_functions.py:285-409): every branch is an affine map of
 // (sample, model_output, score, variance_noise), same [B, C, F, H, W] layout for all operands
 struct DdimGeneral {
@@ -473,6 +521,25 @@ extern "C" int mc_cfg_ddim_step_f16(const void* eps_c, const void* eps_u, int ld
     MC_LAUNCH(cfg_ddim_kernel, dim3(ew_blocks((long)CL * F * HW)), dim3(256), 0, (hipStream_t)stream,
               (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, (half_t*)out,
               (half_t*)eps_out, k, CL, F, HW);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+extern "C" int mc_cfg_ddim_step_batched_f16(const void* eps_c, const void* eps_u, int ld, const void* x,
+                                            const float* score, void* out, void* eps_out, float cfg, float sqrt_a_t,
+                                            float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev,
+                                            float score_coef, int V, int CL, int F, int HW, void* stream) {
+    if (V <= 0 || CL <= 0 || F <= 0 || HW <= 0 || ld < CL) return MC_ERR_SHAPE;
+    DdimCoef k{cfg, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev, score_coef};
+    const long tokens = (long)V * F * HW;
+    const bool vec4 = CL == 4 && ld % 4 == 0 && ((uintptr_t)eps_c | (uintptr_t)eps_u) % 8 == 0;
+    if (vec4)
+        MC_LAUNCH(cfg_ddim_batched_kernel<true>, dim3(ew_blocks(tokens)), dim3(256), 0, (hipStream_t)stream,
+                  (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, (half_t*)out,
+                  (half_t*)eps_out, k, V, CL, F, HW);
+    else
+        MC_LAUNCH(cfg_ddim_batched_kernel<false>, dim3(ew_blocks(tokens)), dim3(256), 0, (hipStream_t)stream,
+                  (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, (half_t*)out,
+                  (half_t*)eps_out, k, V, CL, F, HW);
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
 }
 

@@ -748,7 +748,13 @@ class UNet3DEngine:
     @ops.scoped
     def extract_representation(self, noisy_latents, t, uncond_text, down_residuals=None, mid_residual=None):
         """model part of obtain_motion_representation (motionclone_functions.py:74-79): partial forward to the
-        guidance block, P = softmax(scale q k^T) of the hooked temporal attentions, top-1 value/index."""
+        guidance block, P = softmax(scale q k^T) of the hooked temporal attentions, top-1 value/index.
+        V > 1 reference videos (noisy_latents [V, 4, F, H, W], uncond_text [V, n, dim], residuals of the V-element batch):
+        ONE partial forward and one top-1 launch per hooked attention over V times the rows (the read-out is independent
+        per (video, pixel, head) row); returns a list of V representations, views of the batched result."""
+        V = noisy_latents.shape[0]
+        if uncond_text.shape[0] != V:
+            raise ValueError("extract_representation: %d videos need uncond_text [%d, ...], got %s" % (V, V, tuple(uncond_text.shape)))
         record = {}
         self.forward(noisy_latents, t, uncond_text, record=record, only_motion_feature=True,
                      down_residuals=down_residuals, mid_residual=mid_residual)
@@ -758,6 +764,10 @@ class UNet3DEngine:
             C, g = r["C"], r["geo"]
             val, idx = ops.tattn_top1(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, r["heads"], r["d"])
             rep[name] = [val, idx]
+        if V > 1:
+            return [{name: [val[v * (val.shape[0] // V):(v + 1) * (val.shape[0] // V)],
+                            idx[v * (idx.shape[0] // V):(v + 1) * (idx.shape[0] // V)]] for name, (val, idx) in rep.items()}
+                    for v in range(V)]
         return rep
 
     def prepare_representation(self, rep):
@@ -784,14 +794,15 @@ class UNet3DEngine:
         (residuals, if any, are then the B = 2 SparseCtrl outputs).
 
         V > 1 videos at once (latents [V, 4, F, H, W], text_* [V, n, dim], `rep_dev` = prepare_representation of the list of
-        their representations; needs text_uncond): ONE B = 2 V forward over [u_1 .. u_V | c_1 .. c_V], the tape differentiates
-        the conditional halves; every video's loss is its own mean (the seed coefficient uses the per-video element count), so
+        their representations): with text_uncond ONE B = 2 V forward over [u_1 .. u_V | c_1 .. c_V], the tape differentiates
+        the conditional halves; without it one B = V forward over [c_1 .. c_V], all of it differentiated (the sampler's
+        batch_guided=False).  Every video's loss is its own mean (the seed coefficient uses the per-video element count), so
         each video gets exactly the gradient of its separate call.
         Returns (eps_c tokens, grad fp32 [V,4,F,H,W], loss (summed over the videos) or None[, eps_u tokens])."""
         batched = text_uncond is not None
         V = latents.shape[0]
-        if V > 1 and not batched:
-            raise ValueError("several videos per call need text_uncond (one [u_1 .. u_V | c_1 .. c_V] forward)")
+        if text_cond.shape[0] != V:
+            raise ValueError("guided_eps_and_grad: %d videos need text_cond [%d, ...], got %s" % (V, V, tuple(text_cond.shape)))
         tape = Tape(grad_batch=(V, 2 * V) if batched else None)
         # The loss is a MEAN over the attention maps (F.mse_loss, :229), so the gradient per element shrinks with the size of
         # the problem: 4e-5 at the latent for config 2, 6e-6 for config 5 (32 f x 96^2), where `grad_scale` = 1024 left the deep
@@ -853,14 +864,20 @@ class ControlNetEngine(UNet3DEngine):
         return names + ["mid_block.resnets.0.", "mid_block.resnets.1."]
 
     def _cond_embedding(self, cond, mask, F, H, W):
-        """controlnet_cond_embedding(cat(cond, mask)) + conv_in.bias (:516-527) as a token matrix [(f y x), C0].
+        """controlnet_cond_embedding(cat(cond, mask)) + conv_in.bias (:516-527) as a token matrix [(v f y x), C0] for the
+        Vc = cond.shape[0] condition videos (every conv sees Vc F independent frames: one launch sequence for all of them).
         latent_condition.yaml: one 3x3 conv on VAE latent + mask at latent resolution.  image_condition.yaml (scribble /
         sketch): SparseControlNetConditioningEmbedding (:49-82) on pixels + mask at 8x the latent resolution - conv_in,
         then (same-width, stride-2 widening) conv pairs down to the latent grid, SiLU after each, conv_out; every conv an
         implicit GEMM on 64-padded channels-last rows (padding channels stay zero through SiLU).  Recomputed at every call,
         as in the reference."""
         w = self.w
+        if mask.shape[0] != cond.shape[0]:
+            if mask.shape[0] != 1:
+                raise ValueError("condition batch %d vs mask batch %d" % (cond.shape[0], mask.shape[0]))
+            mask = mask.expand(cond.shape[0], -1, -1, -1, -1)
         cm = torch.cat([cond, mask], dim=1).to(torch.float16)
+        NF = cm.shape[0] * F          # frames of all the condition videos: one launch sequence covers them
         p = "controlnet_cond_embedding."
         cin_b = w.vec("conv_in.bias")
         if (p + "weight") in w.sd:
@@ -868,7 +885,7 @@ class ControlNetEngine(UNet3DEngine):
                 raise ValueError("latent condition %s does not match the sample grid %s" % (tuple(cm.shape), (F, H, W)))
             bias = (w.vec(p + "bias") + cin_b).unsqueeze(0).contiguous()
             e = ops.gemm(ops.latent_to_cl(cm, CIN_PAD), w.conv(p + "weight", CIN_PAD), bias=bias, mode=CONV_S1,
-                         geom=(H, W, H, W), m_out=F * H * W)
+                         geom=(H, W, H, W), m_out=NF * H * W)
         else:
             Hs, Ws = cm.shape[3], cm.shape[4]
             nblk = 0
@@ -882,7 +899,7 @@ class ControlNetEngine(UNet3DEngine):
                 last = name == "conv_out."
                 cout = w.sd[p + name + "weight"].shape[0]
                 Ho, Wo = (Hs, Ws) if stride == 1 else (Hs // 2, Ws // 2)
-                rows, cpad = F * Ho * Wo, (cout + 63) // 64 * 64
+                rows, cpad = NF * Ho * Wo, (cout + 63) // 64 * 64
                 buf = (torch.zeros if cpad != cout else torch.empty)((rows, cpad), dtype=torch.float16, device=self.dev)
                 b = w.vec(p + name + "bias")
                 ops.gemm(x, w.conv(p + name + "weight", pad_cin=x.shape[1]),
@@ -893,25 +910,46 @@ class ControlNetEngine(UNet3DEngine):
             e = x
         return e
 
+    @staticmethod
+    def batch_layout(B, Vc):
+        """(V, halves) of a batch of B elements fed by Vc conditions: the batch is `halves` groups of V videos, group-major
+        ([u_1 .. u_V | c_1 .. c_V] for halves = 2, the V videos of an extraction for halves = 1), video v of every group takes
+        condition v.  Vc == 1: the same condition for every element (an even batch is then read as two groups, which all
+        hold the same rows in front of the first cross-attention)."""
+        if Vc == 1:
+            return (B // 2, 2) if B % 2 == 0 else (B, 1)
+        if B == Vc:
+            return Vc, 1
+        if B == 2 * Vc:
+            return Vc, 2
+        raise ValueError("SparseCtrl: %d conditions for a batch of %d (need 1, the batch, or half the [u | c] batch)" % (Vc, B))
+
     @ops.scoped
     def forward(self, sample_shape, t, text, cond, mask, conditioning_scale=1.0):
-        """sample_shape = (B, 4, F, H, W); cond [1, Cc, F, H, W] latent condition (or [1, 3, F, 8H, 8W] pixels for the
-        scribble embedding; zeros on unconditioned frames), mask [1, 1, F, ...] at the condition's resolution;
-        text [B, n, dim] -> (list of 12 residual token matrices [(b f y x), C], mid residual)"""
+        """sample_shape = (B, 4, F, H, W); cond [Vc, Cc, F, H, W] latent condition (or [Vc, 3, F, 8H, 8W] pixels for the
+        scribble embedding; zeros on unconditioned frames), mask [Vc, 1, F, ...] at the condition's resolution;
+        text [B, n, dim] -> (list of 12 residual token matrices [(b f y x), C], mid residual).
+        B = 2 V ordered [u_1 .. u_V | c_1 .. c_V] (a step) or B = V (an extraction) with Vc = V conditions - the embedding is
+        computed once per video and video v's u and c elements share it - or Vc = 1: the same condition for every element."""
         cfg, w = self.cfg, self.w
         B, _, F, H, W = sample_shape
         L = cfg["layers_per_block"]
         geo = Geo(B, F, H, W)
+        if text.shape[0] != B:
+            raise ValueError("SparseCtrl: text %s for a batch of %d" % (tuple(text.shape), B))
+        Vc = cond.shape[0]
+        V, halves = self.batch_layout(B, Vc)
         n_text = text.shape[1]
         text2d = text.reshape(B * n_text, text.shape[2]).contiguous()
         tb_all = self._time_bias(t, B, text)
         e = self._cond_embedding(cond, mask, F, H, W)
-        # the same condition for every batch element: the batch elements differ in their text only, so (as in
-        # UNet3DEngine.forward(dup=True)) what precedes the first cross-attention runs once for a [u | c] batch
-        share = self.share_prefix and B == 2 and cfg["down_has_attn"][0]
-        geoA = Geo(1, F, H, W) if share else None
-        feats = [torch.cat([e] * B, dim=0) if B > 1 else e]
-        x = e if share else feats[0]
+        eV = e if Vc == V else torch.cat([e] * V, dim=0)       # one group of V videos
+        # the groups differ in their text only, so (as in UNet3DEngine.forward(dup=True)) what precedes the first
+        # cross-attention runs once on the V elements of a [u_1 .. u_V | c_1 .. c_V] batch
+        share = self.share_prefix and halves == 2 and cfg["down_has_attn"][0]
+        geoA = Geo(V, F, H, W) if share else None
+        feats = [torch.cat([eV] * halves, dim=0) if halves > 1 else eV]
+        x = eV if share else feats[0]
         for i in range(4):
             for j in range(L):
                 if share and i == 0 and j == 0:
@@ -938,9 +976,10 @@ class ControlNetEngine(UNet3DEngine):
         return down, mid
 
 
-def split_residuals(down, mid, b, B):
-    """rows of batch element b out of B from every residual (the reference's tensor[[b], ...], :205-208)"""
+def split_residuals(down, mid, b, B, count=1):
+    """rows of the batch elements [b, b + count) out of B from every residual (the reference's tensor[[b], ...], :205-208;
+    count = V cuts the u half [0, V) or the c half [V, 2 V) of a packed [u_1 .. u_V | c_1 .. c_V] batch)"""
     def rows(t):
         n = t.shape[0] // B
-        return t[b * n:(b + 1) * n]
+        return t[b * n:(b + count) * n]
     return [rows(d) for d in down], rows(mid)

@@ -680,19 +680,28 @@ def ddim_step_general(sample, model_output, score, noise, coef, want_prev=True, 
 
 
 def cfg_ddim_step(eps_c, eps_u, x, score, cfg, a_t, a_prev, score_coef, want_eps=False, sigma=0.0):
-    """x, score: [1, CL, F, H, W]; eps_*: channels-last token matrices (first CL columns).  sigma = eta * sqrt(variance)
-    of schedule_customized_step (:364-365): the direction coefficient becomes sqrt(1 - a_prev - sigma^2) (:386); the
-    caller adds sigma * noise (:391-405)."""
-    B, CL, F, H, W = x.shape
-    if B != 1 or (score is not None and tuple(score.shape) != tuple(x.shape)):
-        raise ValueError("cfg_ddim_step updates one video per call: x %s, score %s" % (tuple(x.shape), None if score is None else tuple(score.shape)))
+    """x, score: [V, CL, F, H, W]; eps_*: channels-last token matrices [(v f y x), ld] (first CL columns), video-major.
+    sigma = eta * sqrt(variance) of schedule_customized_step (:364-365): the direction coefficient becomes
+    sqrt(1 - a_prev - sigma^2) (:386); the caller adds sigma * noise (:391-405).  V == 1 is mc_cfg_ddim_step_f16, V > 1 ONE
+    launch of mc_cfg_ddim_step_batched_f16 (per video bit-identical to its own V == 1 call)."""
+    V, CL, F, H, W = x.shape
+    if V < 1 or (score is not None and tuple(score.shape) != tuple(x.shape)):
+        raise ValueError("cfg_ddim_step: x %s, score %s" % (tuple(x.shape), None if score is None else tuple(score.shape)))
+    if V > 1 and (eps_c.shape[0] != V * F * H * W or eps_u.shape[0] != V * F * H * W):
+        raise ValueError("cfg_ddim_step: %d videos of %d tokens need eps rows [(v f y x)], got %d / %d" % (
+            V, F * H * W, eps_c.shape[0], eps_u.shape[0]))
     x = x.contiguous()
     out = torch.empty_like(x)
     eps_out = torch.empty_like(x) if want_eps else None
     if score is not None:
         score = _f32(score.contiguous())
     assert _ld(eps_c) == _ld(eps_u)
-    lib.call("mc_cfg_ddim_step_f16", _p(eps_c), _p(eps_u), _ld(eps_c), _p(x), _p(score), _p(out), _p(eps_out),
-             float(cfg), float(a_t) ** 0.5, float(1.0 - a_t) ** 0.5, float(a_prev) ** 0.5,
-             max(float(1.0 - a_prev) - float(sigma) ** 2, 0.0) ** 0.5, float(score_coef), CL, F, H * W, _stream(x))
+    coefs = (float(cfg), float(a_t) ** 0.5, float(1.0 - a_t) ** 0.5, float(a_prev) ** 0.5,
+             max(float(1.0 - a_prev) - float(sigma) ** 2, 0.0) ** 0.5, float(score_coef))
+    if V == 1:
+        lib.call("mc_cfg_ddim_step_f16", _p(eps_c), _p(eps_u), _ld(eps_c), _p(x), _p(score), _p(out), _p(eps_out),
+                 *coefs, CL, F, H * W, _stream(x))
+    else:
+        lib.call("mc_cfg_ddim_step_batched_f16", _p(eps_c), _p(eps_u), _ld(eps_c), _p(x), _p(score), _p(out), _p(eps_out),
+                 *coefs, V, CL, F, H * W, _stream(x))
     return (out, eps_out) if want_eps else out

@@ -116,3 +116,9 @@ class AnimationPipeline:
                 raise ValueError(f"Unexpected latents shape, got {latents.shape}, expected {shape}")
             latents = latents.to(device)
         return latents * self.scheduler.init_noise_sigma
+
+    def sample_video_batch(self, examples, eta=0.0, decode=True):
+        """V examples packed into one launch sequence (motionclone_functions.sample_video_batch); also bindable like the other
+        functions of that module: `pipeline.sample_video_batch = sample_video_batch.__get__(pipeline)`"""
+        from ..utils import motionclone_functions as mf
+        return mf.sample_video_batch(self, examples, eta=eta, decode=decode)

@@ -94,14 +94,30 @@ class MotionCloneSampler:
 
     @ops.scoped
     def extract(self, video_latents, noise, uncond_text, add_noise_step=400, ctrl=None):
-        """ctrl = dict(cond, mask, scale) runs the SparseCtrl encoder first (motionclone_functions.py:46-72)"""
+        """ctrl = dict(cond, mask, scale) runs the SparseCtrl encoder first (motionclone_functions.py:46-72).
+        V > 1 reference videos (video_latents / noise [V, 4, F, H, W], uncond_text [V, n, dim] or [1, n, dim] for all of them,
+        ctrl batched as in `_step_eager`): ONE partial forward, one top-1 launch per hooked attention; a list of V
+        representations comes back."""
+        V = video_latents.shape[0]
+        if uncond_text.shape[0] != V:
+            if uncond_text.shape[0] != 1:
+                raise ValueError("extract: %d videos, uncond_text %s" % (V, tuple(uncond_text.shape)))
+            uncond_text = uncond_text.expand(V, -1, -1).contiguous()
         noisy = self.add_noise(add_noise_step, video_latents, noise)
         if ctrl is None:
             return self.engine.extract_representation(noisy, add_noise_step, uncond_text)
+        self._check_ctrl(ctrl, V)
         down, mid = self.controlnet.forward(tuple(noisy.shape), add_noise_step, uncond_text, ctrl["cond"], ctrl["mask"],
                                             ctrl.get("scale", 1.0))
         return self.engine.extract_representation(noisy, add_noise_step, uncond_text, down_residuals=down,
                                                   mid_residual=mid)
+
+    @staticmethod
+    def _check_ctrl(ctrl, V):
+        nc, nm = ctrl["cond"].shape[0], ctrl["mask"].shape[0]
+        if nc not in (1, V) or nm not in (1, nc):
+            raise ValueError("SparseCtrl condition batch must be 1 (the same for every video) or %d (one per video): cond %s, "
+                             "mask %s" % (V, tuple(ctrl["cond"].shape), tuple(ctrl["mask"].shape)))
 
     # ---- hipGraph replay of whole steps (SURVEY.md 8(f) rank 4: step-loop host overhead) ----------------------------
     def enable_graphs(self):
@@ -118,7 +134,7 @@ class MotionCloneSampler:
         the replay, so a graph captured on the first video serves every later (prompt, reference-video) pair."""
         guided = i < self.G
         rsig = tuple((k, tuple(v[0].shape)) for k, v in rep_dev.items()) if guided else ()
-        csig = None if ctrl is None else (tuple(ctrl["cond"].shape), float(ctrl.get("scale", 1.0)))
+        csig = None if ctrl is None else (tuple(ctrl["cond"].shape), tuple(ctrl["mask"].shape), float(ctrl.get("scale", 1.0)))
         key = (i, tuple(latents.shape), tuple(text.shape), rsig, csig, self._gemm_share())   # the GEMM geometry is baked in
         ent = self._graphs.get(key)
         if ent is None:
@@ -200,27 +216,23 @@ class MotionCloneSampler:
         layout); rep_dev: engine.prepare_representation of the V representations (a list for V > 1).  V > 1 = V independent
         videos through ONE launch sequence (same kernels, V times the rows): each video's arithmetic is its own - no
         reduction crosses the batch - but the GEMM tile / split-K choice follows the larger row count, so results agree
-        with the one-video path to fp16 rounding, not bit for bit."""
+        with the one-video path to fp16 rounding, not bit for bit.  ctrl: `cond` [V, ...] / `mask` [V, 1, ...] carry one
+        SparseCtrl condition per video ([1, ...]: the same one for all); with batch_guided=False the uncond forward and the
+        differentiated cond forward each run on V elements with their halves of the encoder's residuals."""
         from .engine import split_residuals
         eng = self.engine
         V = latents.shape[0]
         if text.shape[0] != 2 * V:
             raise ValueError("text must hold [uncond x V | cond x V] embeddings: %s for %d videos" % (tuple(text.shape), V))
-        if V > 1 and (ctrl is not None or not self.batch_guided):
-            raise NotImplementedError("several videos per step: not with SparseCtrl / batch_guided=False")
         t, a_t, a_prev = self._alphas(i)
         down = mid = None
         if ctrl is not None:
-            shape2 = (2,) + tuple(latents.shape[1:])
+            self._check_ctrl(ctrl, V)
+            shape2 = (2 * V,) + tuple(latents.shape[1:])
             down, mid = self.controlnet.forward(shape2, t, text, ctrl["cond"], ctrl["mask"], ctrl.get("scale", 1.0))
 
-        def update(eps_c, eps_u, grad, coef):
-            if V == 1:
-                return ops.cfg_ddim_step(eps_c, eps_u, latents, grad, self.cfg_scale, a_t, a_prev, coef, sigma=sigma)
-            T1 = eps_c.shape[0] // V           # the fused CFG + DDIM update works on one video's rows at a time
-            return torch.cat([ops.cfg_ddim_step(eps_c[v * T1:(v + 1) * T1], eps_u[v * T1:(v + 1) * T1], latents[v:v + 1],
-                                                None if grad is None else grad[v:v + 1], self.cfg_scale, a_t, a_prev, coef,
-                                                sigma=sigma) for v in range(V)], 0)
+        def update(eps_c, eps_u, grad, coef):     # one launch for the V videos (V = 1: the one-video entry, as ever)
+            return ops.cfg_ddim_step(eps_c, eps_u, latents, grad, self.cfg_scale, a_t, a_prev, coef, sigma=sigma)
         if i < self.G:
             w = self.weight * self.guidance_factor(i)
             if self.batch_guided:
@@ -230,11 +242,11 @@ class MotionCloneSampler:
                                                                    mid_residual=mid, text_uncond=text[:V])
             else:
                 du = mu = dc = mc = None
-                if down is not None:
-                    du, mu = split_residuals(down, mid, 0, 2)
-                    dc, mc = split_residuals(down, mid, 1, 2)
-                eps_u = eng.forward(latents, t, text[0:1], down_residuals=du, mid_residual=mu)
-                eps_c, grad, loss = eng.guided_eps_and_grad(latents, t, text[1:2], rep_dev, w, want_loss=aux is not None,
+                if down is not None:      # the u half [0, V) and the c half [V, 2 V) of the encoder's batch
+                    du, mu = split_residuals(down, mid, 0, 2 * V, V)
+                    dc, mc = split_residuals(down, mid, V, 2 * V, V)
+                eps_u = eng.forward(latents, t, text[:V], down_residuals=du, mid_residual=mu)
+                eps_c, grad, loss = eng.guided_eps_and_grad(latents, t, text[V:], rep_dev, w, want_loss=aux is not None,
                                                             down_residuals=dc, mid_residual=mc)
             if aux is not None:
                 aux.update(eps_u=eps_u, eps_c=eps_c, grad=grad, loss=loss)
@@ -259,6 +271,22 @@ class MotionCloneSampler:
         return latents
 
 
+def batch_ctrl(entry, V):
+    """the SparseCtrl argument of ONE job of V videos as one dict: None / a dict (already batched: cond [V, ...] or [1, ...])
+    pass through; a list of V per-video dicts (cond [1, ...] each, one common conditioning scale) is concatenated in video
+    order"""
+    if entry is None or isinstance(entry, dict):
+        return entry
+    if len(entry) != V:
+        raise ValueError("SparseCtrl: %d per-video conditions for a job of %d videos" % (len(entry), V))
+    if V == 1:
+        return entry[0]
+    scales = {float(c.get("scale", 1.0)) for c in entry}
+    if len(scales) != 1:
+        raise ValueError("SparseCtrl: the videos of one batched job share one conditioning scale, got %s" % sorted(scales))
+    return dict(cond=torch.cat([c["cond"] for c in entry], 0), mask=torch.cat([c["mask"] for c in entry], 0), scale=scales.pop())
+
+
 def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=None, on_step=None):
     """Several independent videos in flight on one GPU (examples are the unit of parallelism).
 
@@ -270,7 +298,9 @@ def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=No
     (callers that keep 2 lanes busy set it to 2 once, before any graph is captured: the GEMM tile / split-K choice then
     targets half of the CUs per launch, +3.6 % videos/min).  `on_step(k, i, enter)` is called around every
     step inside the lane's stream context (bench.py records its events there).  `streams=None` issues everything on the
-    current stream (same issue order, no overlap; what the host-simulator tests use).  Returns the final latents per job."""
+    current stream (same issue order, no overlap; what the host-simulator tests use).  `ctrl`: one SparseCtrl dict for every
+    job, or a LIST with one entry per job - a dict, or for a batched job a list of per-video dicts / an already batched dict
+    (`batch_ctrl`).  Returns the final latents per job."""
     n = len(jobs)
     if n == 0:
         return []
@@ -284,20 +314,29 @@ def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=No
         cur = torch.cuda.current_stream(first[0].device)
         for st in streams[:n]:
             st.wait_stream(cur)
-    xs, reps, texts = [None] * n, [None] * n, [None] * n
+    if isinstance(ctrl, (list, tuple)) and len(ctrl) != n:
+        raise ValueError("sample_interleaved: %d ctrl entries for %d jobs" % (len(ctrl), n))
+    xs, reps, texts, ctrls = [None] * n, [None] * n, [None] * n, [None] * n
     for k, job in enumerate(jobs):
         vids = job if isinstance(job, list) else [job]       # a LIST of videos on one lane = one batched launch sequence
         with lane(k):
-            rr = [samplers[k].extract(vid, noise, text[0:1], add_noise_step=add_noise_step, ctrl=ctrl) for (_, text, vid, noise) in vids]
-            reps[k] = samplers[k].engine.prepare_representation(rr if len(vids) > 1 else rr[0])
-            xs[k] = vids[0][0] if len(vids) == 1 else torch.cat([v[0] for v in vids], 0)
-            texts[k] = vids[0][1] if len(vids) == 1 else torch.cat([v[1][0:1] for v in vids] + [v[1][1:2] for v in vids], 0)
+            ctrls[k] = batch_ctrl(ctrl[k] if isinstance(ctrl, (list, tuple)) else ctrl, len(vids))
+            if len(vids) == 1:
+                (x, text, vid, noise), = vids
+                rr = samplers[k].extract(vid, noise, text[0:1], add_noise_step=add_noise_step, ctrl=ctrls[k])
+                xs[k], texts[k] = x, text
+            else:                 # one partial forward + one top-1 launch per hooked attention for the lane's V videos
+                rr = samplers[k].extract(torch.cat([v[2] for v in vids], 0), torch.cat([v[3] for v in vids], 0),
+                                         torch.cat([v[1][0:1] for v in vids], 0), add_noise_step=add_noise_step, ctrl=ctrls[k])
+                xs[k] = torch.cat([v[0] for v in vids], 0)
+                texts[k] = torch.cat([v[1][0:1] for v in vids] + [v[1][1:2] for v in vids], 0)
+            reps[k] = samplers[k].engine.prepare_representation(rr)
     for i in range(len(samplers[0].timesteps)):
         for k in range(n):
             with lane(k):
                 if on_step is not None:
                     on_step(k, i, True)
-                xs[k] = samplers[k].step(xs[k], i, texts[k], reps[k], ctrl=ctrl)
+                xs[k] = samplers[k].step(xs[k], i, texts[k], reps[k], ctrl=ctrls[k])
                 if on_step is not None:
                     on_step(k, i, False)
     if streams is not None:

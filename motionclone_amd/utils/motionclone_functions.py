@@ -238,6 +238,144 @@ def sample_video(self, eta: float = 0.0, generator=None, noisy_latents: Optional
     return self.decode_latents(noisy_latents)
 
 
+def _condition_images(pipe, ex):
+    """what `sample_video` turns `controlnet_images` / `condition_image_path_list` into (:112-128) for one example"""
+    cfg = pipe.input_config
+    if ex.get("controlnet_images") is not None:
+        return ex["controlnet_images"]
+    from PIL import Image
+    import numpy as _np
+    imgs = []
+    for path in ex.get("condition_image_path_list", getattr(cfg, "condition_image_path_list", None)):
+        im = Image.open(path).convert("RGB").resize((cfg.width, cfg.height), Image.BILINEAR)
+        imgs.append(torch.from_numpy(_np.array(im)).permute(2, 0, 1).float() / 255.0)
+    px = torch.stack(imgs).to(dtype=pipe.vae.dtype, device=pipe.vae.device)
+    if pipe.controlnet.use_simplified_condition_embedding:
+        lat = pipe.vae.encode(px * 2.0 - 1.0).latent_dist.sample() * pipe.vae.config.scaling_factor
+        return lat.unsqueeze(0).permute(0, 2, 1, 3, 4).contiguous()
+    return px.unsqueeze(0).permute(0, 2, 1, 3, 4).contiguous()
+
+
+def _placed(src, idx, frames=None):
+    """condition tensor + mask with `src`'s frames at image_index `idx` (:46-72,176-197); src already holds `frames` frames
+    (the reference video itself) or only the condition frames"""
+    shape = list(src.shape)
+    if frames is not None:
+        shape[2] = frames
+    cond = torch.zeros(shape, device=src.device, dtype=src.dtype)
+    mask = torch.zeros([shape[0], 1] + shape[2:], device=src.device, dtype=src.dtype)
+    cond[:, :, idx] = src[:, :, idx] if frames is None else src
+    mask[:, :, idx] = 1
+    return cond, mask
+
+
+@torch.no_grad()
+def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
+    """V examples through ONE packed launch sequence (the way to the packed regime from the pipeline API): what
+    `obtain_motion_representation` + `sample_video` do for one example, for a list of V dicts.  Each dict carries one example's
+    arguments of those two functions: `new_prompt` (+ `negative_prompt`) or `text_embeddings` [2, n, dim]; `video_latents` or
+    `video_path` / `video_data` (+ `duration`); `uncond_embeddings` (optional); `noisy_latents` or `generator`; for
+    image-to-video `controlnet_images` or `condition_image_path_list` (either one turns SparseCtrl on; all examples or none).
+    Returns a list of V results, each what `sample_video(decode=...)` returns for that example.
+
+    Host work (VAE posterior draw, extraction noise, condition-image VAE draw, CLIP, latent prior) runs per example in list
+    order, in the order the two functions run it, from the example's generator: the draws are those of V sequential calls.
+    The extraction is one partial forward for the V reference videos, every DDIM step one launch sequence over V times the
+    rows (hipGraph replay as in `single_step_video`); `eta > 0` takes the eager steps, the variance noise drawn per video in
+    list order at every step.  V = 1 is the two functions themselves."""
+    cfg = self.input_config
+    V = len(examples)
+    if V == 0:
+        return []
+    use_ctrl = [ex.get("controlnet_images") is not None or ex.get("condition_image_path_list") is not None for ex in examples]
+    if any(use_ctrl) != all(use_ctrl):
+        raise ValueError("sample_video_batch: either every example carries a condition image or none does")
+    use_ctrl = use_ctrl[0]
+    if V == 1:
+        ex = examples[0]
+        old = {k: getattr(cfg, k) for k in ("new_prompt", "negative_prompt", "video_path", "condition_image_path_list")
+               if k in ex and hasattr(cfg, k)}
+        try:
+            for k in old:
+                setattr(cfg, k, ex[k])
+            self.obtain_motion_representation(generator=ex.get("generator"), duration=ex.get("duration"), use_controlnet=use_ctrl,
+                                              video_latents=ex.get("video_latents"), uncond_embeddings=ex.get("uncond_embeddings"),
+                                              video_data=ex.get("video_data"))
+            return [self.sample_video(eta=eta, generator=ex.get("generator"), noisy_latents=ex.get("noisy_latents"),
+                                      add_controlnet=use_ctrl, text_embeddings=ex.get("text_embeddings"), decode=decode,
+                                      controlnet_images=ex.get("controlnet_images"))]
+        finally:
+            for k, v in old.items():
+                setattr(cfg, k, v)
+    smp = _sampler(self)
+    device = self._execution_device
+    step_t = int(cfg.add_noise_step)
+    vids, noises, unconds, texts, lats, ext_c, ext_m, smp_c, smp_m = ([] for _ in range(9))
+    for ex in examples:                      # host work, example by example in the order of the sequential calls
+        gen = ex.get("generator")
+        video_latents, video_data = ex.get("video_latents"), ex.get("video_data")
+        if video_latents is None:            # obtain_motion_representation (:25-44)
+            if video_data is None:
+                video_data = video_preprocess(ex.get("video_path", getattr(cfg, "video_path", None)), cfg.height, cfg.width,
+                                              cfg.video_length, duration=ex.get("duration"))
+            lat = self.vae.encode(video_data.to(self.vae.dtype).to(self.vae.device)).latent_dist.sample(None)
+            video_latents = (self.vae.config.scaling_factor * lat).unsqueeze(0).permute(0, 2, 1, 3, 4).contiguous()
+        uncond = ex.get("uncond_embeddings")
+        if uncond is None:
+            tok = self.tokenizer([""], padding="max_length", max_length=self.tokenizer.model_max_length, return_tensors="pt")
+            uncond = self.text_encoder(tok.input_ids.to(self.device))[0]
+        noises.append(torch.randn(video_latents.shape, generator=gen, device=video_latents.device, dtype=video_latents.dtype))
+        vids.append(video_latents)
+        unconds.append(uncond.to(video_latents.device))
+        if use_ctrl:
+            if self.controlnet.use_simplified_condition_embedding:
+                src = video_latents
+            else:
+                if video_data is None:
+                    raise ValueError("the pixel-condition SparseCtrl needs the preprocessed frames (video_data)")
+                src = ((video_data.unsqueeze(0).to(video_latents.device, video_latents.dtype).permute(0, 2, 1, 3, 4) + 1) / 2)
+            c, m = _placed(src, cfg.image_index)
+            ext_c.append(c)
+            ext_m.append(m)
+            ci = _condition_images(self, ex).to(device, torch.float16)           # sample_video (:112-128)
+            c, m = _placed(ci, cfg.image_index, frames=cfg.video_length)
+            smp_c.append(c)
+            smp_m.append(m)
+        text = ex.get("text_embeddings")
+        if text is None:
+            text = self._encode_prompt(ex.get("new_prompt", getattr(cfg, "new_prompt", None)), device, 1, True,
+                                       ex.get("negative_prompt", getattr(cfg, "negative_prompt", None)))
+        texts.append(text)
+        lats.append(self.prepare_latents(1, self.unet.config.in_channels, cfg.video_length, cfg.height, cfg.width, text.dtype,
+                                         device, gen, ex.get("noisy_latents")))
+    ext_ctrl = ctrl = None
+    if use_ctrl:
+        smp.controlnet = self.controlnet.engine()
+        ext_ctrl = dict(cond=torch.cat(ext_c, 0).half(), mask=torch.cat(ext_m, 0).half(), scale=cfg.controlnet_scale)
+        ctrl = dict(cond=torch.cat(smp_c, 0), mask=torch.cat(smp_m, 0), scale=cfg.controlnet_scale)
+    reps = smp.extract(torch.cat(vids, 0).half(), torch.cat(noises, 0).half(), torch.cat(unconds, 0).half(),
+                       add_noise_step=step_t, ctrl=ext_ctrl)
+    rep_dev = smp.engine.prepare_representation(reps)
+    x = torch.cat(lats, 0).half()
+    text2 = torch.cat([t[0:1] for t in texts] + [t[1:2] for t in texts], 0).half()
+    with self.progress_bar(total=cfg.inference_steps) as progress_bar:
+        for i in range(len(smp.timesteps)):
+            if eta:
+                z = []
+                for v, ex in enumerate(examples):
+                    gen = ex.get("generator")
+                    gdev = gen.device if gen is not None else x.device
+                    z.append(torch.randn(x[v:v + 1].shape, generator=gen, device=gdev, dtype=x.dtype).to(x.device))
+                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl, eta=float(eta), variance_noise=torch.cat(z, 0))
+            else:
+                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl)
+            progress_bar.update()
+    x = x.detach()
+    if not decode:
+        return [x[v:v + 1].clone() for v in range(V)]     # (a replayed step hands out the graph's static buffer: copies)
+    return [self.decode_latents(x[v:v + 1]) for v in range(V)]
+
+
 @torch.no_grad()
 def schedule_customized_step(self, model_output, step_index: int, sample, eta: float = 0.0,
                              use_clipped_model_output: bool = False, generator=None, variance_noise=None,
