@@ -41,5 +41,5 @@ def read(path):
     if _shared is None:
         return _read_file(path)
     from . import lanes
-    leader = lanes.lane_index() in (None, 0)
+    leader = lanes.lane_index() in (None, 0) and not lanes.slot_index()      # one thread per process
     return _copy_containers(_shared.load(os.path.abspath(path), lambda: _read_file(path), is_leader=leader))

@@ -22,7 +22,21 @@ before it.  With `--serial-rng` (default on) a rank burns, for every line it ski
 (one `[L, 4, H/8, W/8]` normal tensor for the reference video, plus `[n_images, 4, H/8, W/8]` for i2v condition images),
 so that the sharded run reproduces the single-process run bit for bit.  Lanes shard the same way (line i -> rank i mod world,
 lane (i div world) mod K) and each lane keeps a PRIVATE copy of the "global" stream (lanes.py), so `--lanes K` is bit-identical
-to the serial run as well (tests/test_entry_scripts.py)."""
+to the serial run as well (tests/test_entry_scripts.py).
+
+`--batch V` (default 1): every lane carries GROUPS of V examples through ONE packed launch sequence (V times the rows per kernel;
+`MotionCloneSampler._step_eager` on [V, 4, F, H, W], replayed from hipGraphs) - the regime bench.py's headline is measured in
+(`--lanes 2 --batch 5`), reached by the unmodified scripts.  A process then runs K V script threads, one per (lane, slot): with
+n = i div world, line i goes to slot n mod V of lane (n div V) mod K, as group n div (V K) of that lane (`assign`), so a group is
+V consecutive lines of the rank.  Every thread walks the script on its own lines with its own private serial stream and its own
+models (K V copies of the checkpoints on the GPU); its `obtain_motion_representation` is the one-video extraction, so the
+representations stay bit-identical to the serial run.  In `sample_video` the V threads of a lane meet (lanes.Group): the one with
+the lowest live slot runs the packed step loop for all of them in the lane's stream and hands each its final latents, which
+each decodes itself.  Packed steps agree with one-video steps to fp16 rounding (5e-3 relative L2 over the loop,
+tests/test_packed_dropin_api.py), not bit for bit.  A thread without a further line leaves its group: the last group of a lane
+runs with the members that are left, a lone member runs the plain one-video `sample_video`.  A thread that raises releases
+every thread waiting for it, and the launcher exits with the first error.  Representations go to
+`<dir>/rank<r>_lane<l>_slot<s>/`."""
 import argparse
 import builtins
 import io
@@ -85,21 +99,29 @@ def _condition_images_are_encoded(inference_config):
         return True
 
 
-class _ShardedLines(io.StringIO):
-    """file object over the examples file that yields only this rank's lines; before each of them it burns the global-RNG
-    draws of the lines skipped since the previous one (see module docstring)"""
+def assign(i, world=1, n_lanes=1, batch=1):
+    """(rank, lane, slot, group number within the lane) of line i of the examples file"""
+    n = i // world
+    return i % world, (n // batch) % n_lanes, n % batch, n // (batch * n_lanes)
 
-    def __init__(self, lines, rank, world, burn, first_begin=None, first_end=None):
+
+class _ShardedLines(io.StringIO):
+    """file object over the examples file that yields only the lines `owns(i)` holds for (default: i mod world == rank); before
+    each of them it burns the global-RNG draws of the lines skipped since the previous one (see module docstring)"""
+
+    def __init__(self, lines, rank, world, burn, first_begin=None, first_end=None, owns=None, on_end=None):
         super().__init__("")
         self._items = [(i, ln) for i, ln in enumerate(lines) if ln.strip()]
-        self._rank, self._world, self._burn = rank, world, burn
+        self._owns = owns if owns is not None else (lambda i: i % world == rank)
+        self._burn = burn
         self._first_begin, self._first_end = first_begin, first_end     # lanes: the first example of a lane runs alone
+        self._on_end = on_end                                           # groups: no further line, the thread leaves its group
 
     def __iter__(self):
         n = 0
         try:
             for i, ln in self._items:
-                if i % self._world == self._rank:
+                if self._owns(i):
                     if n == 0 and self._first_begin:
                         self._first_begin()
                     if n == 1 and self._first_end:       # asked for the second line = the first example is finished
@@ -109,6 +131,8 @@ class _ShardedLines(io.StringIO):
                 elif self._burn is not None:
                     self._burn(json.loads(ln))
         finally:
+            if self._on_end:                             # first: the fellow members must not wait for this thread any more
+                self._on_end()
             if n == 0 and self._first_begin:             # a lane without examples still takes its turn
                 self._first_begin()
             if n <= 1 and self._first_end:
@@ -135,6 +159,13 @@ def main(argv=None):
     if "--lanes" in argv:
         i = argv.index("--lanes")
         del argv[i:i + 2]
+    batch = int(_arg(argv, ["--batch"], 1))
+    if "--batch" in argv:
+        i = argv.index("--batch")
+        del argv[i:i + 2]
+    if n_lanes < 1 or batch < 1:
+        raise SystemExit("--lanes and --batch must be at least 1")
+    n_threads = n_lanes * batch
     script, sargv = argv[0], argv[1:]
     # Pin the GPU BEFORE anything initialises the HIP runtime: the runtime reads CUDA_VISIBLE_DEVICES once, and both
     # torch.cuda.is_available() and the scripts' own late `os.environ["CUDA_VISIBLE_DEVICES"] = args.visible_gpu` (inside
@@ -174,34 +205,39 @@ def main(argv=None):
         if n_img:
             torch.randn((n_img, 4, H // vae_scale, W // vae_scale), device=dev, dtype=torch.float16, generator=gen)
 
-    # virtual rank of (rank, lane): line i belongs to it iff i mod (world K) == rank + world lane
-    vworld = world * n_lanes
-    sharded = vworld > 1
+    # line i belongs to the thread (rank, lane, slot) that `assign` names; batch == 1: iff i mod (world K) == rank + world lane
+    sharded = world * n_threads > 1
     real_open = builtins.open
     ex_abs = os.path.abspath(examples)
 
     def sharded_open(path, *a, **k):
         if sharded and isinstance(path, (str, os.PathLike)) and os.path.abspath(path) == ex_abs and (not a or "r" in a[0]):
-            vrank = rank + world * (mcl.lane_index() or 0)
-            fb, fe = (warm_begin, warm_end) if n_lanes > 1 else (None, None)
-            if n_lanes > 1:      # the lane has built its models (their H2D copies synchronise): it is ready for the warm-up turns
+            me = (rank, mcl.lane_index() or 0, mcl.slot_index() or 0)
+            fb, fe = (warm_begin, warm_end) if n_threads > 1 else (None, None)
+            if n_threads > 1:    # the thread has built its models (their H2D copies synchronise): it is ready for the warm-up turns
                 with warm_turn:
                     warm_state["ready"] += 1
                     warm_turn.notify_all()
-            return _ShardedLines(lines, vrank, vworld, burn if serial_rng else None, fb, fe)
+            grp, slot = mcl.group(), mcl.slot_index()
+            return _ShardedLines(lines, rank, world, burn if serial_rng else None, fb, fe,
+                                 owns=lambda i: assign(i, world, n_lanes, batch)[:3] == me,
+                                 on_end=(lambda: grp.leave(slot)) if grp is not None else None)
         return real_open(path, *a, **k)
 
     # A lane's FIRST example runs alone: it captures the lane's step graphs, and ROCm 7.2 rejects synchronising calls of any
     # other host thread while a capture is open.  Turns are taken in lane order; when every lane has had its turn they all
     # continue concurrently (replays only; lanes.may_capture).
-    # No lane takes its turn before EVERY lane has opened the examples file, i.e. has finished load_state_dict / .to(cuda):
-    # those are synchronising calls too and would hit lane 0's open capture otherwise.  A lane that dies releases the others.
+    # No lane takes its turn before EVERY thread has opened the examples file, i.e. has finished load_state_dict / .to(cuda):
+    # those are synchronising calls too and would hit lane 0's open capture otherwise.  A thread that dies releases the others.
+    # With --batch V the lane's first GROUP takes the turn: its V threads enter it together, do their host work (VAE encode,
+    # CLIP: synchronising calls, all before any capture opens), meet, and are parked at the meeting point while the leader
+    # captures the packed steps.  The turn ends when each of the V has asked for its second line (or has none).
     warm_turn = threading.Condition()
-    warm_state = dict(turn=0, ready=0)
+    warm_state = dict(turn=0, ready=0, ended=0)
 
     def warm_begin():
         with warm_turn:
-            warm_turn.wait_for(lambda: errors or (warm_state["ready"] >= n_lanes
+            warm_turn.wait_for(lambda: errors or (warm_state["ready"] >= n_threads
                                                   and warm_state["turn"] == (mcl.lane_index() or 0)))
             if errors:
                 raise RuntimeError("lane %d failed: %r" % errors[0])
@@ -209,16 +245,24 @@ def main(argv=None):
     def warm_end():
         if on_gpu:
             torch.cuda.current_stream().synchronize()
+            grp = mcl.group()
+            if grp is not None and grp.stream is not None:
+                grp.stream.synchronize()
         mcl.warmed_up()
         with warm_turn:
-            warm_state["turn"] += 1
+            warm_state["ended"] += 1
+            if warm_state["ended"] == batch:     # only the lane whose turn it is has threads between begin and end
+                warm_state["ended"] = 0
+                warm_state["turn"] += 1
             warm_turn.notify_all()
             warm_turn.wait_for(lambda: errors or warm_state["turn"] >= n_lanes)
 
-    def lane_argv(lane):
+    def lane_argv(lane, slot=0):
         out = sargv
         if sharded:
             sub = "rank%d" % rank if n_lanes == 1 else "rank%d_lane%d" % (rank, lane)
+            if batch > 1:
+                sub = "rank%d_lane%d_slot%d" % (rank, lane, slot)
             out = _set_arg(out, "--motion-representation-save-dir", os.path.join(rep_dir, sub))
         return out
 
@@ -226,7 +270,7 @@ def main(argv=None):
     # process share them (checkpoints.py / dist.SharedCheckpoints).  The scripts' own direct torch.load calls (the SparseCtrl
     # checkpoint, i2v_video_sample.py) go the same way; the per-example motion-representation files do not.
     from . import checkpoints as mck
-    share_ckpt = broadcast_weights and (world > 1 or n_lanes > 1)
+    share_ckpt = broadcast_weights and (world > 1 or n_threads > 1)
     real_torch_load = torch.load
     rep_abs = os.path.abspath(rep_dir)
 
@@ -247,21 +291,27 @@ def main(argv=None):
 
     errors = []
 
-    def run_lane(lane):
+    groups = [mcl.Group(batch) if batch > 1 else None for _ in range(n_lanes)]
+
+    def run_lane(lane, slot=0):
         try:
-            if n_lanes > 1:
-                mcl.begin(lane, n_lanes, "cuda" if on_gpu else "cpu")
+            if n_threads > 1:
+                mcl.begin(lane, n_lanes, "cuda" if on_gpu else "cpu", slot=slot, group=groups[lane])
                 if on_gpu:
                     torch.cuda.set_stream(torch.cuda.Stream())
-            targv.argv = lane_argv(lane)
+            targv.argv = lane_argv(lane, slot)
             runpy.run_path(script, run_name="__main__")
             if on_gpu:
                 torch.cuda.current_stream().synchronize()
         except BaseException as e:   # noqa: BLE001 - reported by the main thread
             errors.append((lane, e))
+            if groups[lane] is not None:     # fellow members at the meeting point re-raise it
+                groups[lane].fail(e)
             with warm_turn:          # lanes waiting for their warm-up turn must not wait for a dead one
                 warm_turn.notify_all()
         finally:
+            if groups[lane] is not None:
+                groups[lane].leave(slot)
             mcl.end()
 
     builtins.open = sharded_open
@@ -274,12 +324,14 @@ def main(argv=None):
     t0 = time.perf_counter()
     try:
         sys.argv = [script] + lane_argv(0)
-        if n_lanes == 1:
+        if n_threads == 1:
             run_lane(0)
         else:
-            from . import ops
-            ops.set_gemm_share(n_lanes)     # tile / split-K choice for n_lanes launch sequences in flight (before any graph capture)
-            threads = [threading.Thread(target=run_lane, args=(k,), name="lane%d" % k) for k in range(n_lanes)]
+            if n_lanes > 1:
+                from . import ops
+                ops.set_gemm_share(n_lanes)     # tile / split-K choice for n_lanes launch sequences in flight (before any graph capture)
+            threads = [threading.Thread(target=run_lane, args=(k, s), name="lane%d" % k if batch == 1 else "lane%d_slot%d" % (k, s))
+                       for k in range(n_lanes) for s in range(batch)]
             for t in threads:
                 t.start()
             for t in threads:
@@ -297,7 +349,7 @@ def main(argv=None):
     slowest = mcd.max_over_ranks(dt, device="cuda" if on_gpu and world > 1 else "cpu")
     if rank == 0:
         n = len([ln for ln in lines if ln.strip()])
-        print(json.dumps(dict(examples=n, world=world, lanes=n_lanes, seconds=slowest, videos_per_min=60.0 * n / slowest,
+        print(json.dumps(dict(examples=n, world=world, lanes=n_lanes, batch=batch, seconds=slowest, videos_per_min=60.0 * n / slowest,
                               examples_of_rank0=[i for i, _ in mine],
                               checkpoint_files_read_by_rank0=shared.reads if shared else None)))
     elif shared is not None:

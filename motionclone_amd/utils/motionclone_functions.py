@@ -228,11 +228,17 @@ def sample_video(self, eta: float = 0.0, generator=None, noisy_latents: Optional
     if isinstance(getattr(self, "motion_representation_path", None), str) and os.path.exists(self.motion_representation_path):
         self.motion_representation_dict = torch.load(self.motion_representation_path)
     self.motion_scale = cfg.motion_guidance_weight
-    extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)
-    with self.progress_bar(total=cfg.inference_steps) as progress_bar:
-        for step_index, step_t in enumerate(self.scheduler.timesteps):
-            noisy_latents = self.single_step_video(noisy_latents, step_index, step_t, extra_step_kwargs)
-            progress_bar.update()
+    from .. import lanes
+    grp = lanes.group()
+    packed = _group_sample(self, grp, noisy_latents, eta, generator) if grp is not None and grp.size > 1 else None
+    if packed is not None:     # the thread's lane carried this example through one packed launch sequence with its fellows'
+        noisy_latents = packed
+    else:
+        extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)
+        with self.progress_bar(total=cfg.inference_steps) as progress_bar:
+            for step_index, step_t in enumerate(self.scheduler.timesteps):
+                noisy_latents = self.single_step_video(noisy_latents, step_index, step_t, extra_step_kwargs)
+                progress_bar.update()
     if not decode:
         return noisy_latents
     return self.decode_latents(noisy_latents)
@@ -269,6 +275,101 @@ def _placed(src, idx, frames=None):
     return cond, mask
 
 
+_MIXED = "either every example carries a condition image or none does"
+
+
+@torch.no_grad()
+def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None):
+    """The packed step loop on this pipeline's sampler for V videos whose per-example host work is done: `latents` V tensors
+    [1, 4, F, H, W], `texts` V [2, n, dim] ([uncond, cond]), `reps` V motion representations, `ctrls` V SparseCtrl dicts
+    (cond / mask [1, ...] placed at image_index, scale) or V times None, `generators` the V generators that `eta > 0` draws each
+    video's variance noise from, in list order at every step.  Returns the final latents [V, 4, F, H, W] - after a replayed
+    step the graph's static buffer: callers that keep them copy."""
+    from ..sampler import batch_ctrl
+    cfg = self.input_config
+    V = len(latents)
+    use_ctrl = [c is not None for c in ctrls]
+    if any(use_ctrl) != all(use_ctrl):
+        raise ValueError("sample_video_batch: " + _MIXED)
+    smp = _sampler(self)
+    ctrl = None
+    if use_ctrl[0]:
+        smp.controlnet = self.controlnet.engine()
+        ctrl = batch_ctrl(list(ctrls), V)
+    rep_dev = smp.engine.prepare_representation(list(reps))
+    x = torch.cat(list(latents), 0).half()
+    text2 = torch.cat([t[0:1] for t in texts] + [t[1:2] for t in texts], 0).half()
+    with self.progress_bar(total=cfg.inference_steps) as progress_bar:
+        for i in range(len(smp.timesteps)):
+            if eta:
+                z = []
+                for v in range(V):
+                    gen = generators[v] if generators is not None else None
+                    gdev = gen.device if gen is not None else x.device
+                    z.append(torch.randn(x[v:v + 1].shape, generator=gen, device=gdev, dtype=x.dtype).to(x.device))
+                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl, eta=float(eta), variance_noise=torch.cat(z, 0))
+            else:
+                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl)
+            progress_bar.update()
+    return x.detach()
+
+
+def _run_group(grp, items):
+    """the leader's part of the meeting point: the live members' examples through ONE packed launch sequence on the leader's
+    pipeline, in the lane's stream; every member gets (a copy of its [1, 4, F, H, W] slice, the event that marks it complete).
+    A lone member gets None: it runs the one-video loop itself."""
+    if len(items) == 1:
+        return [None]
+    etas = {it["eta"] for it in items}
+    if len(etas) != 1:
+        raise ValueError("the examples of one packed group share one eta, got %s" % sorted(etas))
+    pipe = items[0]["pipe"]
+    on_gpu = items[0]["latents"].is_cuda
+
+    def run():
+        x = _packed_sample(pipe, [it["latents"] for it in items], [it["text"] for it in items], [it["rep"] for it in items],
+                           [it["ctrl"] for it in items], eta=etas.pop(), generators=[it["generator"] for it in items])
+        return [x[v:v + 1].clone() for v in range(len(items))]
+    if not on_gpu:
+        return [(o, None) for o in run()]
+    if grp.stream is None:
+        grp.stream = torch.cuda.Stream()
+    for it in items:
+        grp.stream.wait_event(it["ready"])
+    with torch.cuda.stream(grp.stream):
+        outs = run()
+        done = torch.cuda.Event()
+        done.record()
+    return [(o, done) for o in outs]
+
+
+def _group_sample(self, grp, noisy_latents, eta, generator):
+    """`sample_video` inside a launcher lane that carries several examples (`motionclone_amd.launch --batch V`): the host work
+    of this example is done; bring it to the lane's group, wait for the fellow members, and take this example's final latents
+    from the packed run (None: no fellow is left, the caller runs the one-video loop)."""
+    from .. import lanes
+    cfg = self.input_config
+    ctrl = None
+    if self.add_controlnet:      # what single_step_video places at image_index (:176-197)
+        ci = self.controlnet_images.to(noisy_latents.device, torch.float16)
+        cond, mask = _placed(ci, cfg.image_index, frames=noisy_latents.shape[2])
+        ctrl = dict(cond=cond, mask=mask, scale=cfg.controlnet_scale)
+    ready = None
+    if noisy_latents.is_cuda:
+        ready = torch.cuda.Event()
+        ready.record()
+    item = dict(pipe=self, latents=noisy_latents, text=self.text_embeddings, rep=self.motion_representation_dict, ctrl=ctrl,
+                eta=float(eta or 0.0), generator=generator, ready=ready)
+    out = grp.meet(lanes.slot_index(), item, lambda items: _run_group(grp, items))
+    if out is None:
+        return None
+    x, done = out
+    if done is not None:         # computed in the lane's stream, consumed (decoded) in this thread's
+        torch.cuda.current_stream().wait_event(done)
+        x.record_stream(torch.cuda.current_stream())
+    return x
+
+
 @torch.no_grad()
 def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
     """V examples through ONE packed launch sequence (the way to the packed regime from the pipeline API): what
@@ -289,7 +390,7 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
         return []
     use_ctrl = [ex.get("controlnet_images") is not None or ex.get("condition_image_path_list") is not None for ex in examples]
     if any(use_ctrl) != all(use_ctrl):
-        raise ValueError("sample_video_batch: either every example carries a condition image or none does")
+        raise ValueError("sample_video_batch: " + _MIXED)
     use_ctrl = use_ctrl[0]
     if V == 1:
         ex = examples[0]
@@ -348,29 +449,15 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
         texts.append(text)
         lats.append(self.prepare_latents(1, self.unet.config.in_channels, cfg.video_length, cfg.height, cfg.width, text.dtype,
                                          device, gen, ex.get("noisy_latents")))
-    ext_ctrl = ctrl = None
+    ext_ctrl = None
+    ctrls = [None] * V
     if use_ctrl:
         smp.controlnet = self.controlnet.engine()
         ext_ctrl = dict(cond=torch.cat(ext_c, 0).half(), mask=torch.cat(ext_m, 0).half(), scale=cfg.controlnet_scale)
-        ctrl = dict(cond=torch.cat(smp_c, 0), mask=torch.cat(smp_m, 0), scale=cfg.controlnet_scale)
+        ctrls = [dict(cond=c, mask=m, scale=cfg.controlnet_scale) for c, m in zip(smp_c, smp_m)]
     reps = smp.extract(torch.cat(vids, 0).half(), torch.cat(noises, 0).half(), torch.cat(unconds, 0).half(),
                        add_noise_step=step_t, ctrl=ext_ctrl)
-    rep_dev = smp.engine.prepare_representation(reps)
-    x = torch.cat(lats, 0).half()
-    text2 = torch.cat([t[0:1] for t in texts] + [t[1:2] for t in texts], 0).half()
-    with self.progress_bar(total=cfg.inference_steps) as progress_bar:
-        for i in range(len(smp.timesteps)):
-            if eta:
-                z = []
-                for v, ex in enumerate(examples):
-                    gen = ex.get("generator")
-                    gdev = gen.device if gen is not None else x.device
-                    z.append(torch.randn(x[v:v + 1].shape, generator=gen, device=gdev, dtype=x.dtype).to(x.device))
-                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl, eta=float(eta), variance_noise=torch.cat(z, 0))
-            else:
-                x = smp.step(x, i, text2, rep_dev, ctrl=ctrl)
-            progress_bar.update()
-    x = x.detach()
+    x = _packed_sample(self, lats, texts, reps, ctrls, eta=eta, generators=[ex.get("generator") for ex in examples])
     if not decode:
         return [x[v:v + 1].clone() for v in range(V)]     # (a replayed step hands out the graph's static buffer: copies)
     return [self.decode_latents(x[v:v + 1]) for v in range(V)]
