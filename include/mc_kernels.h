@@ -209,6 +209,10 @@ int mc_tattn_fwd_f16(const void* q, const void* k, const void* v, int ld, void* 
 /* motionclone_functions.py:260-283 + torch.topk(k=1) of :79 -> top_val fp16 / top_idx u8, [B*HW, heads, F] */
 int mc_tattn_top1_f16(const void* q, const void* k, int ld, void* top_val, void* top_idx, int B, int F, int HW,
                       int heads, int d, float scale, void* stream);
+/* the same read-out for torch.topk(k = K), 1 <= K <= min(F, 8) (else MC_ERR_SHAPE, nothing launched): top_val fp16 / top_idx u8
+ * [B*HW, heads, F, K], descending, equal fp16 probabilities by ascending frame index.  K = 1 gives mc_tattn_top1_f16's bits. */
+int mc_tattn_topk_f16(const void* q, const void* k, int ld, void* top_val, void* top_idx, int K, int B, int F, int HW,
+                      int heads, int d, float scale, void* stream);
 /* get_temp_attn_prob (motionclone_functions.py:260-283): prob fp16 [B*HW, heads, F, F] */
 int mc_tattn_prob_f16(const void* q, const void* k, int ld, void* prob, int B, int F, int HW, int heads, int d,
                       float scale, void* stream);
@@ -217,11 +221,21 @@ int mc_tattn_prob_f16(const void* q, const void* k, int ld, void* prob, int B, i
 int mc_tattn_loss_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val,
                       float* unit_loss, float* loss, int B, int F, int HW, int heads, int d, float scale,
                       void* stream);
+/* the same for a top-k representation: ref_idx u8 / ref_val f32 [B*HW, heads, F, K], loss[0] = the mean over all
+ * B*HW*heads*F*K entries (F.mse_loss of gather(P, idx) [.., F, K]); unit_loss as above; K as for mc_tattn_topk_f16 */
+int mc_tattn_loss_topk_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val, int K,
+                           float* unit_loss, float* loss, int B, int F, int HW, int heads, int d, float scale,
+                           void* stream);
 /* data-gradient of the attention (dO may be NULL) fused with the guidance seed
  * dP[q, idx[q]] += seed_coef * (P[q, idx[q]] - ref[q]) (ref_idx may be NULL): motionclone_functions.py:236 */
 int mc_tattn_bwd_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo, void* dq,
                      void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, float seed_coef,
                      int B, int F, int HW, int heads, int d, float scale, void* stream);
+/* mc_tattn_bwd_f16 with K seeds per query row (ref_idx / ref_val [B*HW, heads, F, K], both required):
+ * dP[q, idx[q][j]] += seed_coef * (P[q, idx[q][j]] - ref[q][j]) for every j < K; a frame named twice in a row gets both */
+int mc_tattn_bwd_topk_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo, void* dq,
+                          void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, int K,
+                          float seed_coef, int B, int F, int HW, int heads, int d, float scale, void* stream);
 int mc_reduce_sum_f32(const float* in, long n, float scale, float* out, void* stream);
 
 /* ---- element-wise glue ------------------------------------------------------------------------ */

@@ -15,6 +15,10 @@
 // The backward kernel fuses: recompute P, the guidance-loss seed
 // dP[q, idx[q]] += coef * (P[q, idx[q]] - ref[q]), softmax backward, and the three
 // operand gradients; both tile orientations are produced by swapping MFMA operands.
+// Sparsity k of the motion representation (torch.topk(k) of :79; the reference's consumer :85-100 takes any k): the kernels
+// carry a template bound KM on the seeds per query row.  KM = 1 is the code of the k = 1 entry points, instruction for
+// instruction; KM = MC_TATTN_KMAX serves 1 <= K <= KM of the *_topk entries with the K indices / references of a row in
+// registers (loops over j < KM fully unrolled, left at the first j >= K, which is uniform).
 #include "mc_common.hpp"
 #include <cstdlib>
 
@@ -34,6 +38,8 @@ __device__ __forceinline__ f32x4 mfma16z(half4_t a, half4_t b, f32x4 c) { return
 #ifndef MC_TATTN_PROBE
 #define MC_TATTN_PROBE 0
 #endif
+
+constexpr int MC_TATTN_KMAX = 8;   // largest k of the top-k read-out / loss / seed (8 one-byte indices per query row)
 
 struct TParams {
     const half_t* q;
@@ -162,11 +168,14 @@ __device__ __forceinline__ void t_softmax_T(f32x4 (&st)[NT], float& m, float& l)
 // ---- forward --------------------------------------------------------------------------------
 // mode 0: write attention output o; mode 1: write top-1 (value fp16, index u8) of P per query;
 // mode 2: write the per-query squared error (P[q, idx[q]] - ref[q])^2 summed per unit.
-template <int NT, int DT>
+// KM > 1 (modes 1 and 2 only): K = Krt values / indices per query, [.., F, K] - mode 1 the K largest fp16 probabilities in
+// descending order, equal ones by ascending frame; mode 2 the squared errors of all K entries of a row.
+template <int NT, int DT, int KM = 1>
 __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, int ldo, int mode,
                                                          half_t* top_val, uint8_t* top_idx,
                                                          const uint8_t* ref_idx, const float* ref_val,
-                                                         float* unit_loss) {
+                                                         float* unit_loss, int Krt) {
+    const int K = KM == 1 ? 1 : Krt;
     const int lane = threadIdx.x & 63;
     TUnit u = t_unit(P);
     if (!u.live) return;  // whole wave
@@ -210,6 +219,51 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
                 hi = group_sum(hi);
                 l = (double)lo + (double)hi;
             }
+            if constexpr (KM > 1) {
+                // K rounds of the top-1 selection below on the lane's fp16 probabilities; the lane that owns the winner of
+                // a round retires it (probabilities are >= 0, so -1 never wins while K <= F valid ones exist)
+                float pq[NT][4];
+#pragma unroll
+                for (int tk = 0; tk < NT; ++tk)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        int kv = 16 * tk + 4 * (lane >> 4) + i;
+                        pq[tk][i] = kv < P.F ? (float)(half_t)(float)(ed[tk][i] / l) : -1.f;
+                    }
+#pragma unroll
+                for (int j = 0; j < KM; ++j) {
+                    if (j >= K) break;   // uniform
+                    float best = -1.f;
+                    int bi = 0;
+#pragma unroll
+                    for (int tk = 0; tk < NT; ++tk)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (pq[tk][i] > best) {   // ascending kv within the lane: first maximum kept
+                                best = pq[tk][i];
+                                bi = 16 * tk + 4 * (lane >> 4) + i;
+                            }
+#pragma unroll
+                    for (int msk = 16; msk <= 32; msk <<= 1) {
+                        float ob = shfl_xor(best, msk);
+                        int oi = shfl_xor(bi, msk);
+                        if (ob > best || (ob == best && oi < bi)) {
+                            best = ob;
+                            bi = oi;
+                        }
+                    }
+#pragma unroll
+                    for (int tk = 0; tk < NT; ++tk)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (16 * tk + 4 * (lane >> 4) + i == bi) pq[tk][i] = -1.f;
+                    if (lane < 16 && qf < P.F) {
+                        top_val[(unit * P.F + qf) * K + j] = (half_t)best;
+                        top_idx[(unit * P.F + qf) * K + j] = (uint8_t)bi;
+                    }
+                }
+                continue;
+            }
             float best = -1.f;
             int bi = 0;
 #pragma unroll
@@ -245,17 +299,21 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
         t_softmax_T<NT>(st, m, l);
         const float inv = 1.0f / l;
         if (mode == 2) {
-            int idx = qf < P.F ? (int)ref_idx[unit * P.F + qf] : 0;
-            float pv = 0.f;
 #pragma unroll
-            for (int tk = 0; tk < NT; ++tk)
+            for (int j = 0; j < KM; ++j) {
+                if (j >= K) break;   // uniform
+                int idx = qf < P.F ? (int)ref_idx[(unit * P.F + qf) * K + j] : 0;
+                float pv = 0.f;
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (16 * tk + 4 * (lane >> 4) + i == idx) pv = st[tk][i] * inv;
-            pv = group_sum(pv);
-            if (lane < 16 && qf < P.F) {
-                float dlt = pv - ref_val[unit * P.F + qf];
-                loss_acc += dlt * dlt;
+                for (int tk = 0; tk < NT; ++tk)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (16 * tk + 4 * (lane >> 4) + i == idx) pv = st[tk][i] * inv;
+                pv = group_sum(pv);
+                if (lane < 16 && qf < P.F) {
+                    float dlt = pv - ref_val[(unit * P.F + qf) * K + j];
+                    loss_acc += dlt * dlt;
+                }
             }
             continue;
         }
@@ -367,11 +425,14 @@ __global__ __launch_bounds__(256) void tattn_fwd_vec_kernel(TParams P, half_t* o
 // tattn_fwd_vec_kernel: the K = 32 steps add the same products in the same order as the zero-extended K = 16 steps, bit for bit),
 // and Q, K, dO are kept as wave-private row-major LDS images from which the gradient MFMAs take their transposed fragments by
 // ds_read_b64_tr_b16 - 8 load instructions per unit at d = 40 instead of 48 (36 of them two-byte gathers).
-template <int NT, int DT, int VAR = 0, bool VEC = false>
+// KM > 1: K = Krt seeds per query row, ref_idx / ref_val [.., F, K]; the seeds of a row ACCUMULATE in the order of j, so a
+// row that names one frame twice gets both contributions (what gather + autograd gives).
+template <int NT, int DT, int VAR = 0, bool VEC = false, int KM = 1>
 __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t* dO, int lddo, half_t* dq,
                                                          half_t* dk, half_t* dv, int ldg,
                                                          const uint8_t* ref_idx, const float* ref_val,
-                                                         float seed_coef, float* dbg = nullptr) {
+                                                         float seed_coef, float* dbg, int Krt) {
+    const int K = KM == 1 ? 1 : Krt;
     constexpr int NS = (DT + 1) / 2;
     constexpr int PB = 64 * NS + 16;            // VEC: image row pitch, bytes
     constexpr int IMG = 16 * NT * PB;           // one image of one wave
@@ -479,13 +540,17 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 
     // per-query statistics in the transposed orientation (query = 16tq + c15)
     float mq[NT], lq[NT], Dq[NT];
-    int idxq[NT];
-    float refq[NT];
+    int idxq[NT][KM];
+    float refq[NT][KM];
 #pragma unroll
     for (int tq = 0; tq < NT; ++tq) {
         const int qv = 16 * tq + c15;
-        idxq[tq] = (ref_idx && qv < P.F) ? (int)ref_idx[unit * P.F + qv] : -1;
-        refq[tq] = (ref_idx && qv < P.F) ? ref_val[unit * P.F + qv] : 0.f;
+#pragma unroll
+        for (int j = 0; j < KM; ++j) {
+            const bool on = ref_idx && qv < P.F && j < K;
+            idxq[tq][j] = on ? (int)ref_idx[(unit * P.F + qv) * K + j] : -1;
+            refq[tq][j] = on ? ref_val[(unit * P.F + qv) * K + j] : 0.f;
+        }
         float m = -INFINITY;
 #pragma unroll
         for (int tk = 0; tk < NT; ++tk)
@@ -513,7 +578,11 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
                 int kv = 16 * tk + 4 * g + i;
                 float pv = expf(sT[tq][tk][i] - m) / l;
                 float d = dpT[tq][tk][i];
-                if (kv == idxq[tq]) d += seed_coef * (pv - refq[tq]);
+#pragma unroll
+                for (int j = 0; j < KM; ++j) {
+                    if (j >= K) break;   // uniform
+                    if (kv == idxq[tq][j]) d += seed_coef * (pv - refq[tq][j]);
+                }
 #if MC_TATTN_PROBE & 1   // tools/tattn_race.py: which packed-fp32 chain of an SLP build goes wrong (see header)
                 pv = opaque(pv);
 #endif
@@ -544,8 +613,14 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
         for (int i = 0; i < 4; ++i) {
             const int src = 4 * g + i;
             float m = shfl(mq[tq], src), l = shfl(lq[tq], src), D = shfl(Dq[tq], src);
-            int idx = shfl(idxq[tq], src);
-            float rf = shfl(refq[tq], src);
+            int idx[KM];
+            float rf[KM];
+#pragma unroll
+            for (int j = 0; j < KM; ++j) {
+                if (j >= K) break;   // uniform
+                idx[j] = shfl(idxq[tq][j], src);
+                rf[j] = shfl(refq[tq][j], src);
+            }
             const bool qok = 16 * tq + src < P.F;
 #pragma unroll
             for (int tk = 0; tk < NT; ++tk) {
@@ -554,7 +629,11 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
                 if (qok && kv < P.F) {
                     pv = expf(s[tq][tk][i] * P.scale - m) / l;
                     d = dp[tq][tk][i];
-                    if (kv == idx) d += seed_coef * (pv - rf);
+#pragma unroll
+                    for (int j = 0; j < KM; ++j) {
+                        if (j >= K) break;   // uniform
+                        if (kv == idx[j]) d += seed_coef * (pv - rf[j]);
+                    }
                 }
                 pr[tq][tk][i] = (half_t)pv;
                 ds[tq][tk][i] = (half_t)(pv * (d - D));
@@ -564,7 +643,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 
     if constexpr (VAR == 1) {   // tools/race_dump.py: intermediates of tile (0, 0), 24 floats per lane
         float* o = dbg + ((size_t)unit * 64 + lane) * 24;
-        o[0] = mq[0]; o[1] = lq[0]; o[2] = Dq[0]; o[3] = (float)idxq[0]; o[4] = refq[0];
+        o[0] = mq[0]; o[1] = lq[0]; o[2] = Dq[0]; o[3] = (float)idxq[0][0]; o[4] = refq[0][0];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             o[5 + i] = sT[0][0][i];
@@ -642,12 +721,12 @@ static thread_local int g_tattn_last = 0;   // 1: the calling thread's last temp
 static float* g_tattn_debug_buf = nullptr;   // mc_tattn_debug_buffer: intermediates of the F <= 16, d = 40 backward (tools build only)
 #endif
 
-template <int NT, int DT>
+template <int NT, int DT, int KM = 1>
 static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t* tv, uint8_t* ti,
-                         const uint8_t* ri, const float* rv, float* ul, hipStream_t s) {
+                         const uint8_t* ri, const float* rv, float* ul, hipStream_t s, int K = 1) {
     long units = (long)P.B * P.HW * P.heads;
     g_tattn_last = 0;
-    if constexpr (DT == 3 || DT == 5 || DT == 10) {
+    if constexpr (KM == 1 && (DT == 3 || DT == 5 || DT == 10)) {
         // attention output, rows readable 16 bytes at a time (MC_TATTN_VEC=0: the 8-byte kernel, A/B)
         static const int vec_env = MC_ENV_INT("MC_TATTN_VEC", 1);
         const bool aligned = ((uintptr_t)P.q | (uintptr_t)P.k | (uintptr_t)P.v) % 16 == 0;
@@ -657,19 +736,19 @@ static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t*
             return;
         }
     }
-    MC_LAUNCH((tattn_fwd_kernel<NT, DT>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, o, ldo, mode, tv,
-              ti, ri, rv, ul);
+    MC_LAUNCH((tattn_fwd_kernel<NT, DT, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, o, ldo, mode, tv,
+              ti, ri, rv, ul, K);
 }
-template <int NT, int DT>
+template <int NT, int DT, int KM = 1>
 static void t_launch_bwd(const TParams& P, const half_t* dO, int lddo, half_t* dq, half_t* dk, half_t* dv,
-                         int ldg, const uint8_t* ri, const float* rv, float coef, hipStream_t s) {
+                         int ldg, const uint8_t* ri, const float* rv, float coef, hipStream_t s, int K = 1) {
     long units = (long)P.B * P.HW * P.heads;
     g_tattn_last = 0;
 #ifdef MC_TOOLS
-    if constexpr (NT == 1 && DT == 3) {
+    if constexpr (KM == 1 && NT == 1 && DT == 3) {
         if (g_tattn_debug_buf) {
             MC_LAUNCH((tattn_bwd_kernel<NT, DT, 1>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo,
-                      dq, dk, dv, ldg, ri, rv, coef, g_tattn_debug_buf);
+                      dq, dk, dv, ldg, ri, rv, coef, g_tattn_debug_buf, 1);
             return;
         }
     }
@@ -681,15 +760,15 @@ static void t_launch_bwd(const TParams& P, const half_t* dO, int lddo, half_t* d
         constexpr size_t smem = (size_t)4 * 3 * 16 * NT * (64 * NS + 16);
         // (images of at most 48 KiB per workgroup: F <= 16 at d = 40 / 80; beyond that the occupancy lost costs more)
         if (smem <= 48 * 1024 && vec_env && P.d % 8 == 0 && P.ld % 8 == 0 && (!dO || lddo % 8 == 0) && aligned) {
-            allow_big_smem(tattn_bwd_kernel<NT, DT, 0, true>, smem);
-            MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, true>), dim3((unsigned)((units + 3) / 4)), dim3(256), smem, s, P, dO, lddo,
-                      dq, dk, dv, ldg, ri, rv, coef, (float*)nullptr);
+            allow_big_smem(tattn_bwd_kernel<NT, DT, 0, true, KM>, smem);
+            MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, true, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), smem, s, P, dO, lddo,
+                      dq, dk, dv, ldg, ri, rv, coef, (float*)nullptr, K);
             g_tattn_last = 1;
             return;
         }
     }
-    MC_LAUNCH((tattn_bwd_kernel<NT, DT>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo, dq, dk,
-              dv, ldg, ri, rv, coef, (float*)nullptr);
+    MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, false, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo, dq, dk,
+              dv, ldg, ri, rv, coef, (float*)nullptr, K);
 }
 
 #define MC_T_DISPATCH(CALL)                                                     \
@@ -714,6 +793,7 @@ static int t_check(const TParams& P) {
     if (P.d % 4 || P.ld % 4 || P.F > 32) return 0;
     return 1;
 }
+static int t_check_k(const TParams& P, int K) { return K >= 1 && K <= MC_TATTN_KMAX && K <= P.F; }
 
 }  // namespace mc
 
@@ -755,6 +835,21 @@ extern "C" int mc_tattn_top1_f16(const void* q, const void* k, int ld, void* top
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
 }
 
+// top-k motion representation (torch.topk(P_fp16, k = K)): top_val fp16 / top_idx u8 [B*HW, heads, F, K], sorted descending,
+// equal probabilities by ascending frame; 1 <= K <= min(F, 8)
+extern "C" int mc_tattn_topk_f16(const void* q, const void* k, int ld, void* top_val, void* top_idx, int K, int B,
+                                 int F, int HW, int heads, int d, float scale, void* stream) {
+    TParams P = t_params(q, k, k, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_k(P, K)) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                    \
+    t_launch_fwd<NT_, DT_, MC_TATTN_KMAX>(P, nullptr, 0, 1, (half_t*)top_val, (uint8_t*)top_idx, nullptr, nullptr, nullptr, s, K)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
 // motionclone_functions.py:260-283: prob fp16 [B*HW, heads, F, F]
 extern "C" int mc_tattn_prob_f16(const void* q, const void* k, int ld, void* prob, int B, int F, int HW, int heads,
                                  int d, float scale, void* stream) {
@@ -787,6 +882,24 @@ extern "C" int mc_tattn_loss_f16(const void* q, const void* k, int ld, const voi
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
 }
 
+// loss[0] = mean over (unit, frame, j < K) of (P[q, idx[q][j]] - ref[q][j])^2; ref_idx u8 / ref_val f32 [B*HW, heads, F, K]
+extern "C" int mc_tattn_loss_topk_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val,
+                                      int K, float* unit_loss, float* loss, int B, int F, int HW, int heads, int d,
+                                      float scale, void* stream) {
+    TParams P = t_params(q, k, k, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_k(P, K)) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                    \
+    t_launch_fwd<NT_, DT_, MC_TATTN_KMAX>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, unit_loss, s, K)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    long units = (long)B * HW * heads;
+    MC_LAUNCH(reduce_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)unit_loss, units,
+              1.0f / (float)(units * F * K), loss);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
 extern "C" int mc_tattn_bwd_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo,
                                 void* dq, void* dk, void* dv, int ldg, const void* ref_idx,
                                 const float* ref_val, float seed_coef, int B, int F, int HW, int heads, int d,
@@ -799,6 +912,24 @@ extern "C" int mc_tattn_bwd_f16(const void* q, const void* k, const void* v, int
 #define CALL(NT_, DT_)                                                                                        \
     t_launch_bwd<NT_, DT_>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,          \
                            (const uint8_t*)ref_idx, ref_val, seed_coef, s)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// mc_tattn_bwd_f16 with K seeds per query row: dP[q, idx[q][j]] += seed_coef * (P[q, idx[q][j]] - ref[q][j]) for every j < K
+extern "C" int mc_tattn_bwd_topk_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo,
+                                     void* dq, void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val,
+                                     int K, float seed_coef, int B, int F, int HW, int heads, int d, float scale,
+                                     void* stream) {
+    TParams P = t_params(q, k, v, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_k(P, K) || ldg % 4 || (dO && lddo % 4)) return MC_ERR_SHAPE;
+    if (!ref_idx || !ref_val) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                               \
+    t_launch_bwd<NT_, DT_, MC_TATTN_KMAX>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,  \
+                                          (const uint8_t*)ref_idx, ref_val, seed_coef, s, K)
     MC_T_DISPATCH(CALL)
 #undef CALL
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;

@@ -26,6 +26,12 @@ from . import ops
 
 DENSE, CONV_S1, CONV_S2, CONV_UP, TCONV_S2 = ops.DENSE, ops.CONV_S1, ops.CONV_S2, ops.CONV_UP, ops.TCONV_S2
 CIN_PAD = 64
+MAX_TOPK = 8     # largest sparsity k of a motion representation (csrc/temporal.hip MC_TATTN_KMAX)
+
+
+def representation_k(rep_dev):
+    """the top-k sparsity K of a prepared representation {name: (idx [BN, heads, F, K], val)}"""
+    return next(iter(rep_dev.values()))[0].shape[-1] if rep_dev else 1
 
 
 def default_config():
@@ -746,15 +752,19 @@ class UNet3DEngine:
         return [n for n in names if any(blk in n for blk in self.guidance_blocks)]
 
     @ops.scoped
-    def extract_representation(self, noisy_latents, t, uncond_text, down_residuals=None, mid_residual=None):
+    def extract_representation(self, noisy_latents, t, uncond_text, down_residuals=None, mid_residual=None, topk=1):
         """model part of obtain_motion_representation (motionclone_functions.py:74-79): partial forward to the
-        guidance block, P = softmax(scale q k^T) of the hooked temporal attentions, top-1 value/index.
+        guidance block, P = softmax(scale q k^T) of the hooked temporal attentions, top-`topk` values / indices
+        [BN, heads, F, topk] (the reference's producer hard-codes topk = 1; its consumer takes any).
         V > 1 reference videos (noisy_latents [V, 4, F, H, W], uncond_text [V, n, dim], residuals of the V-element batch):
         ONE partial forward and one top-1 launch per hooked attention over V times the rows (the read-out is independent
         per (video, pixel, head) row); returns a list of V representations, views of the batched result."""
         V = noisy_latents.shape[0]
         if uncond_text.shape[0] != V:
             raise ValueError("extract_representation: %d videos need uncond_text [%d, ...], got %s" % (V, V, tuple(uncond_text.shape)))
+        topk = int(topk)
+        if not 1 <= topk <= min(noisy_latents.shape[2], MAX_TOPK):
+            raise ValueError("extract_representation: topk = %d outside 1 .. min(F = %d, %d)" % (topk, noisy_latents.shape[2], MAX_TOPK))
         record = {}
         self.forward(noisy_latents, t, uncond_text, record=record, only_motion_feature=True,
                      down_residuals=down_residuals, mid_residual=mid_residual)
@@ -762,7 +772,10 @@ class UNet3DEngine:
         for name in self.hooked_names():
             r = record[name]
             C, g = r["C"], r["geo"]
-            val, idx = ops.tattn_top1(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, r["heads"], r["d"])
+            if topk == 1:
+                val, idx = ops.tattn_top1(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, r["heads"], r["d"])
+            else:
+                val, idx = ops.tattn_topk(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, r["heads"], r["d"], topk)
             rep[name] = [val, idx]
         if V > 1:
             return [{name: [val[v * (val.shape[0] // V):(v + 1) * (val.shape[0] // V)],
@@ -770,19 +783,40 @@ class UNet3DEngine:
                     for v in range(V)]
         return rep
 
-    def prepare_representation(self, rep):
-        """reference .pt dict {name: [values [BN, heads, F, 1], indices uint8]} -> device tensors for the kernels.
+    def prepare_representation(self, rep, frames=None):
+        """reference .pt dict {name: [values [BN, heads, F, K], indices uint8]} -> device tensors for the kernels; K is the
+        sparsity of the representation (1 in the reference's own files, 1 <= K <= min(F, 8) here), one K for all entries.
         A LIST of such dicts (V videos batched in one forward, guided_eps_and_grad) is concatenated along the (b, pixel) axis
-        in video order - the order of the conditional halves [c_1 .. c_V] in the batch."""
+        in video order - the order of the conditional halves [c_1 .. c_V] in the batch; the V videos share one K.
+        Every entry is validated (ValueError naming the module and the shape): the kernels index [.., F, K] with the K they
+        are told, so a file of another layout would otherwise be read with the wrong stride without any error.
+        `frames`: the video length F of the run, where the caller knows it."""
         if isinstance(rep, (list, tuple)):
-            parts = [self.prepare_representation(r) for r in rep]
+            parts = [self.prepare_representation(r, frames) for r in rep]
             if len(parts) == 1:
                 return parts[0]
+            ks = [representation_k(p) for p in parts]
+            if len(set(ks)) != 1:
+                raise ValueError("the motion representations of one packed batch differ in their top-k: %s" % ks)
             return {name: (torch.cat([p[name][0] for p in parts], 0).contiguous(), torch.cat([p[name][1] for p in parts], 0).contiguous())
                     for name in parts[0]}
         out = {}
         for name, (val, idx) in rep.items():
+            vs, is_ = tuple(val.shape), tuple(idx.shape)
+            if vs != is_:
+                raise ValueError("motion representation %s: values %s and indices %s differ in shape" % (name, vs, is_))
+            if len(vs) != 4:
+                raise ValueError("motion representation %s: shape %s is not [BN, heads, F, K]" % (name, vs))
+            if not 1 <= vs[3] <= min(vs[2], MAX_TOPK):
+                raise ValueError("motion representation %s: shape %s has top-k K = %d outside 1 .. min(F = %d, %d)"
+                                 % (name, vs, vs[3], vs[2], MAX_TOPK))
+            if frames is not None and vs[2] != int(frames):
+                raise ValueError("motion representation %s: shape %s holds %d frames, the run has %d" % (name, vs, vs[2], int(frames)))
             out[name] = (idx.to(self.dev, torch.uint8).contiguous(), val.to(self.dev, torch.float32).contiguous())
+        ks = sorted({i.shape[3] for i, _ in out.values()})
+        if len(ks) > 1:
+            raise ValueError("the entries of one motion representation differ in their top-k: %s"
+                             % {n: tuple(i.shape) for n, (i, _) in out.items()})
         return out
 
     @ops.scoped
@@ -809,11 +843,18 @@ class UNet3DEngine:
         # layers' fp16 gradient activations in the subnormal range (gradient 1.8e-2 from the fp32 oracle against 7e-3 at every
         # smaller size, tests/test_fullsize_parity.py).  The scale therefore follows the map size in powers of two from the
         # validated point (config 2: 32768 elements per hooked attention): exact to undo, same dynamic range at every size.
-        numel_max = max((idx.numel() // V for idx, _ in rep_dev.values()), default=1)
+        # A top-k representation has K entries per attention row and `numel` below counts them all (F.mse_loss's mean), so each
+        # of a row's K seeds is 1 / K of the k = 1 seed: the gradient per ROW stays in the range validated for k = 1.  The scale
+        # therefore follows the number of rows (numel / K); following numel would multiply by K on top of that and spend fp16
+        # headroom for nothing.
+        for name, (idx, _) in rep_dev.items():
+            if idx.dim() != 4 or idx.shape[2] != latents.shape[2]:
+                raise ValueError("motion representation %s: shape %s for a run of %d frames" % (name, tuple(idx.shape), latents.shape[2]))
+        numel_max = max((idx.numel() // idx.shape[-1] // V for idx, _ in rep_dev.values()), default=1)
         tape.grad_scale = self.grad_scale * float(2 ** max(0, round(math.log2(max(1.0, numel_max / 32768.0)))))
         seeds = {}
         for name, (idx, val) in rep_dev.items():
-            numel = idx.numel() // V              # per video: F.mse_loss averages over ONE video's map
+            numel = idx.numel() // V              # per video: F.mse_loss averages over ONE video's map (all K entries per row)
             seeds[name] = (idx, val, tape.grad_scale * float(weight) * 2.0 / numel)
         record = {}
         if batched:

@@ -509,6 +509,29 @@ def tattn_top1(q, k, B, F, HW, heads, d, scale=None):
     return val, idx
 
 
+def tattn_topk(q, k, B, F, HW, heads, d, K, scale=None):
+    """-> (values fp16 [B*HW, heads, F, K], indices uint8 [B*HW, heads, F, K]): torch.topk(P_fp16, k=K) of the reference's
+    producer (:79) - descending, equal probabilities by ascending frame.  1 <= K <= min(F, 8)."""
+    scale = d ** -0.5 if scale is None else scale
+    assert _ld(q) == _ld(k)
+    K = int(K)
+    val = empty((B * HW, heads, F, max(K, 0)), q)
+    idx = empty((B * HW, heads, F, max(K, 0)), q, torch.uint8)
+    lib.call("mc_tattn_topk_f16", _p(q), _p(k), _ld(q), _p(val), _p(idx), K, B, F, HW, heads, d, float(scale),
+             _stream(q))
+    return val, idx
+
+
+def _seed_k(ref_idx, ref_val, BN, heads, F):
+    """sparsity K of a representation [BN, heads, F, K] (legacy [BN, heads, F]: K = 1); values and indices agree in shape"""
+    assert ref_idx.dtype == torch.uint8 and ref_idx.is_contiguous()
+    _f32(ref_val)
+    assert ref_val.shape == ref_idx.shape, "ref_val %s vs ref_idx %s" % (tuple(ref_val.shape), tuple(ref_idx.shape))
+    assert tuple(ref_idx.shape[:3]) == (BN, heads, F) and ref_idx.dim() in (3, 4), \
+        "representation %s for [%d, %d, %d, K]" % (tuple(ref_idx.shape), BN, heads, F)
+    return 1 if ref_idx.dim() == 3 else int(ref_idx.shape[3])
+
+
 def tattn_prob(q, k, B, F, HW, heads, d, scale=None):
     """-> P fp16 [B*HW, heads, F, F] (get_temp_attn_prob, motionclone_functions.py:260-283)"""
     scale = d ** -0.5 if scale is None else scale
@@ -518,13 +541,17 @@ def tattn_prob(q, k, B, F, HW, heads, d, scale=None):
 
 
 def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None):
+    """mean((gather(P, ref_idx) - ref_val)^2) over all entries; the sparsity K is ref_idx.shape[-1]"""
     scale = d ** -0.5 if scale is None else scale
-    assert ref_idx.dtype == torch.uint8 and ref_idx.is_contiguous()
-    _f32(ref_val)
+    K = _seed_k(ref_idx, ref_val, B * HW, heads, F)
     ul = workspace("tattn_loss", q, B, HW, heads)
     loss = empty((1,), q, torch.float32)
-    lib.call("mc_tattn_loss_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), _p(ul), _p(loss), B, F, HW,
-             heads, d, float(scale), _stream(q))
+    if K == 1:
+        lib.call("mc_tattn_loss_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), _p(ul), _p(loss), B, F, HW,
+                 heads, d, float(scale), _stream(q))
+    else:
+        lib.call("mc_tattn_loss_topk_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), K, _p(ul), _p(loss), B, F, HW,
+                 heads, d, float(scale), _stream(q))
     return loss
 
 
@@ -532,9 +559,11 @@ def tattn_bwd(q, k, v, do, dq, dk, dv, B, F, HW, heads, d, ref_idx=None, ref_val
               scale=None):
     scale = d ** -0.5 if scale is None else scale
     assert _ld(q) == _ld(k) == _ld(v) and _ld(dq) == _ld(dk) == _ld(dv)
-    if ref_idx is not None:
-        assert ref_idx.dtype == torch.uint8 and ref_idx.is_contiguous()
-        _f32(ref_val)
+    K = 1 if ref_idx is None else _seed_k(ref_idx, ref_val, B * HW, heads, F)
+    if K != 1:
+        lib.call("mc_tattn_bwd_topk_f16", _p(q), _p(k), _p(v), _ld(q), _p(do), _ld(do), _p(dq), _p(dk), _p(dv), _ld(dq),
+                 _p(ref_idx), _p(ref_val), K, float(seed_coef), B, F, HW, heads, d, float(scale), _stream(q))
+        return
     lib.call("mc_tattn_bwd_f16", _p(q), _p(k), _p(v), _ld(q), _p(do), _ld(do), _p(dq), _p(dk), _p(dv), _ld(dq),
              _p(ref_idx), _p(ref_val), float(seed_coef), B, F, HW, heads, d, float(scale), _stream(q))
 

@@ -93,11 +93,12 @@ class MotionCloneSampler:
         return (a ** 0.5 * x0.float() + (1 - a) ** 0.5 * noise.float()).to(x0.dtype)
 
     @ops.scoped
-    def extract(self, video_latents, noise, uncond_text, add_noise_step=400, ctrl=None):
+    def extract(self, video_latents, noise, uncond_text, add_noise_step=400, ctrl=None, topk=1):
         """ctrl = dict(cond, mask, scale) runs the SparseCtrl encoder first (motionclone_functions.py:46-72).
         V > 1 reference videos (video_latents / noise [V, 4, F, H, W], uncond_text [V, n, dim] or [1, n, dim] for all of them,
-        ctrl batched as in `_step_eager`): ONE partial forward, one top-1 launch per hooked attention; a list of V
-        representations comes back."""
+        ctrl batched as in `_step_eager`): ONE partial forward, one top-k launch per hooked attention; a list of V
+        representations comes back.  `topk`: the sparsity of the representation, values / indices [BN, heads, F, topk]
+        (1 = the reference's producer; the steps infer it from the representation they are given)."""
         V = video_latents.shape[0]
         if uncond_text.shape[0] != V:
             if uncond_text.shape[0] != 1:
@@ -105,12 +106,12 @@ class MotionCloneSampler:
             uncond_text = uncond_text.expand(V, -1, -1).contiguous()
         noisy = self.add_noise(add_noise_step, video_latents, noise)
         if ctrl is None:
-            return self.engine.extract_representation(noisy, add_noise_step, uncond_text)
+            return self.engine.extract_representation(noisy, add_noise_step, uncond_text, topk=topk)
         self._check_ctrl(ctrl, V)
         down, mid = self.controlnet.forward(tuple(noisy.shape), add_noise_step, uncond_text, ctrl["cond"], ctrl["mask"],
                                             ctrl.get("scale", 1.0))
         return self.engine.extract_representation(noisy, add_noise_step, uncond_text, down_residuals=down,
-                                                  mid_residual=mid)
+                                                  mid_residual=mid, topk=topk)
 
     @staticmethod
     def _check_ctrl(ctrl, V):
@@ -151,7 +152,8 @@ class MotionCloneSampler:
                 # for all 30 step indices of every lane is what held 63 GiB reserved for 18 GiB in use (round 3).
                 # the graph key without the step index: a new resolution, batch size or GEMM share setting touches kernels and
                 # GEMM geometries (e.g. the two-workgroup tiles, chosen only for share 0) that have not run eagerly yet
-                kind = (guided, ctrl is not None, tuple(latents.shape), tuple(text.shape), self._gemm_share())
+                # ... and the representation's shapes: another top-k K means other read-out / seed kernels
+                kind = (guided, ctrl is not None, tuple(latents.shape), tuple(text.shape), self._gemm_share(), rsig)
                 if kind not in self._warm_kinds:
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
@@ -263,7 +265,7 @@ class MotionCloneSampler:
         return update(eps2[T1:], eps2[:T1], None, 0.0)
 
     def sample(self, latents, text, rep, progress=None, ctrl=None):
-        rep_dev = self.engine.prepare_representation(rep)
+        rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2])
         for i in range(len(self.timesteps)):
             latents = self.step(latents, i, text, rep_dev, ctrl=ctrl)
             if progress is not None:

@@ -12,6 +12,7 @@ import numpy as np  # noqa: F401
 import torch
 
 from .. import ops
+from ..engine import MAX_TOPK
 from ..sampler import MotionCloneSampler, uneven_timesteps
 from .conv_layer import prep_unet_conv  # noqa: F401
 from .util import classify_blocks, set_all_seed, video_preprocess  # noqa: F401
@@ -81,12 +82,24 @@ def _sampler(pipe):
     return pipe._mc_sampler
 
 
+def _motion_topk(cfg, override=None):
+    """sparsity k of the motion representation to EXTRACT: the optional inference-yaml key `motion_topk` (absent: 1, the
+    reference's torch.topk(k=1) of :79) or a per-call override.  Sampling never reads it: the steps take k from the
+    representation they are given."""
+    k = override if override is not None else getattr(cfg, "motion_topk", None)
+    return 1 if k is None else int(k)
+
+
 @torch.no_grad()
 def obtain_motion_representation(self, generator=None, motion_representation_path: str = None, duration=None,
-                                 use_controlnet=False, video_latents=None, uncond_embeddings=None, video_data=None):
+                                 use_controlnet=False, video_latents=None, uncond_embeddings=None, video_data=None,
+                                 motion_topk=None):
     """:25-82.  `video_latents` / `uncond_embeddings` let synthetic inputs bypass decord / VAE / CLIP (`video_data`
-    [F, 3, H, W] in [-1, 1]: the preprocessed frames, needed beside `video_latents` only by the pixel-condition ControlNet)."""
+    [F, 3, H, W] in [-1, 1]: the preprocessed frames, needed beside `video_latents` only by the pixel-condition ControlNet).
+    `motion_topk` (default: input_config.motion_topk, absent = 1): top-k values / indices per attention row, saved in the
+    reference's layout with last dimension k."""
     cfg = self.input_config
+    topk = _motion_topk(cfg, motion_topk)
     if video_latents is None:
         if video_data is None:
             video_data = video_preprocess(cfg.video_path, cfg.height, cfg.width, cfg.video_length, duration=duration)
@@ -122,10 +135,15 @@ def obtain_motion_representation(self, generator=None, motion_representation_pat
         if "VersatileAttention" in type(module).__name__ and classify_blocks(cfg.motion_guidance_blocks, name):
             r = module.processor.key
             C, g = r["C"], r["geo"]
-            val, idx = ops.tattn_top1(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, module.heads, r["d"])
-            rep[name] = [val, idx]   # topk(k=1) value / uint8 index (:79)
+            if not 1 <= topk <= min(g.F, MAX_TOPK):
+                raise ValueError("motion_topk = %d outside 1 .. min(F = %d, %d)" % (topk, g.F, MAX_TOPK))
+            if topk == 1:
+                val, idx = ops.tattn_top1(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, module.heads, r["d"])
+            else:
+                val, idx = ops.tattn_topk(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, module.heads, r["d"], topk)
+            rep[name] = [val, idx]   # topk(k) value / uint8 index (:79 with k = motion_topk)
     if motion_representation_path is not None:
-        # the reference's on-disk format: {module name: [values fp16 [BN, heads, F, 1], indices uint8 [...]]} (:79-81)
+        # the reference's on-disk format: {module name: [values fp16 [BN, heads, F, k], indices uint8 [...]]} (:79-81)
         torch.save({k: [v.cpu(), i.cpu()] for k, (v, i) in rep.items()}, motion_representation_path)
     self.motion_representation_path = motion_representation_path
     self.motion_representation_dict = rep
@@ -186,7 +204,7 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
         mask[:, :, self.input_config.image_index] = 1
         ctrl = dict(cond=cond, mask=mask, scale=self.input_config.controlnet_scale)
     if getattr(self, "_mc_rep_src", None) is not self.motion_representation_dict:
-        self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict)
+        self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2])
         self._mc_rep_src = self.motion_representation_dict
     kw = dict(extra_step_kwargs or {})      # prepare_extra_step_kwargs: eta / generator, handed to customized_step (:241,255)
     out = smp.step(noisy_latents.half(), step_index, self.text_embeddings.half(), self._mc_rep_dev, ctrl=ctrl,
@@ -296,7 +314,7 @@ def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None):
     if use_ctrl[0]:
         smp.controlnet = self.controlnet.engine()
         ctrl = batch_ctrl(list(ctrls), V)
-    rep_dev = smp.engine.prepare_representation(list(reps))
+    rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2])   # one top-k K for the V videos
     x = torch.cat(list(latents), 0).half()
     text2 = torch.cat([t[0:1] for t in texts] + [t[1:2] for t in texts], 0).half()
     with self.progress_bar(total=cfg.inference_steps) as progress_bar:
@@ -376,7 +394,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
     `obtain_motion_representation` + `sample_video` do for one example, for a list of V dicts.  Each dict carries one example's
     arguments of those two functions: `new_prompt` (+ `negative_prompt`) or `text_embeddings` [2, n, dim]; `video_latents` or
     `video_path` / `video_data` (+ `duration`); `uncond_embeddings` (optional); `noisy_latents` or `generator`; for
-    image-to-video `controlnet_images` or `condition_image_path_list` (either one turns SparseCtrl on; all examples or none).
+    image-to-video `controlnet_images` or `condition_image_path_list` (either one turns SparseCtrl on; all examples or none);
+    `motion_topk` overrides input_config.motion_topk for that example (one value for all the examples of a batch).
     Returns a list of V results, each what `sample_video(decode=...)` returns for that example.
 
     Host work (VAE posterior draw, extraction noise, condition-image VAE draw, CLIP, latent prior) runs per example in list
@@ -401,13 +420,16 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
                 setattr(cfg, k, ex[k])
             self.obtain_motion_representation(generator=ex.get("generator"), duration=ex.get("duration"), use_controlnet=use_ctrl,
                                               video_latents=ex.get("video_latents"), uncond_embeddings=ex.get("uncond_embeddings"),
-                                              video_data=ex.get("video_data"))
+                                              video_data=ex.get("video_data"), motion_topk=ex.get("motion_topk"))
             return [self.sample_video(eta=eta, generator=ex.get("generator"), noisy_latents=ex.get("noisy_latents"),
                                       add_controlnet=use_ctrl, text_embeddings=ex.get("text_embeddings"), decode=decode,
                                       controlnet_images=ex.get("controlnet_images"))]
         finally:
             for k, v in old.items():
                 setattr(cfg, k, v)
+    topks = [_motion_topk(cfg, ex.get("motion_topk")) for ex in examples]
+    if len(set(topks)) != 1:
+        raise ValueError("the motion representations of one packed batch differ in their top-k: %s" % topks)
     smp = _sampler(self)
     device = self._execution_device
     step_t = int(cfg.add_noise_step)
@@ -456,7 +478,7 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
         ext_ctrl = dict(cond=torch.cat(ext_c, 0).half(), mask=torch.cat(ext_m, 0).half(), scale=cfg.controlnet_scale)
         ctrls = [dict(cond=c, mask=m, scale=cfg.controlnet_scale) for c, m in zip(smp_c, smp_m)]
     reps = smp.extract(torch.cat(vids, 0).half(), torch.cat(noises, 0).half(), torch.cat(unconds, 0).half(),
-                       add_noise_step=step_t, ctrl=ext_ctrl)
+                       add_noise_step=step_t, ctrl=ext_ctrl, topk=topks[0])
     x = _packed_sample(self, lats, texts, reps, ctrls, eta=eta, generators=[ex.get("generator") for ex in examples])
     if not decode:
         return [x[v:v + 1].clone() for v in range(V)]     # (a replayed step hands out the graph's static buffer: copies)

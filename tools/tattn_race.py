@@ -40,7 +40,7 @@ VARIANTS = {
     "slp_sum": ["-DMC_TATTN_PROBE=4"],
     "slp_all": ["-DMC_TATTN_PROBE=7"],
 }
-KERNEL = "_ZN2mc16tattn_bwd_kernelILi1ELi3ELi0E"
+KERNEL = "_ZN2mc16tattn_bwd_kernelILi1ELi3ELi0ELb0ELi1EE"
 
 
 def lib_path(name):
