@@ -236,6 +236,20 @@ int mc_tattn_bwd_f16(const void* q, const void* k, const void* v, int ld, const 
 int mc_tattn_bwd_topk_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo, void* dq,
                           void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, int K,
                           float seed_coef, int B, int F, int HW, int heads, int d, float scale, void* stream);
+/* region-weighted guidance: row_w f32 [B*HW, F] (required), the weight of query frame f at (b, pixel) in the order of the
+ * representation's BN axis, shared by the heads; key frames are not weighted.  1 <= K <= min(F, 8), K = 1 included
+ * (ref_idx / ref_val [B*HW, heads, F, K]); any other K or a NULL row_w: MC_ERR_SHAPE, nothing launched.
+ * loss[0] = 1 / (B*HW*heads*F*K) * sum row_w[bn, f] * (P[q, idx[q][j]] - ref[q][j])^2 - the UNWEIGHTED denominator, so
+ * weights of 1 give the bits of mc_tattn_loss_f16 (K = 1) / mc_tattn_loss_topk_f16 (K > 1) */
+int mc_tattn_loss_weighted_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val, int K,
+                               const float* row_w, float* unit_loss, float* loss, int B, int F, int HW, int heads, int d,
+                               float scale, void* stream);
+/* dP[q, idx[q][j]] += seed_coef * row_w[bn, q] * (P[q, idx[q][j]] - ref[q][j]); dO may be NULL, ref_idx / ref_val required;
+ * weights of 1 give the bits of mc_tattn_bwd_f16 (K = 1) / mc_tattn_bwd_topk_f16 (K > 1) */
+int mc_tattn_bwd_weighted_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo, void* dq,
+                              void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, int K,
+                              const float* row_w, float seed_coef, int B, int F, int HW, int heads, int d, float scale,
+                              void* stream);
 int mc_reduce_sum_f32(const float* in, long n, float scale, float* out, void* stream);
 
 /* ---- element-wise glue ------------------------------------------------------------------------ */

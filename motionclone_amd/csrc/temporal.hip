@@ -19,6 +19,10 @@
 // carry a template bound KM on the seeds per query row.  KM = 1 is the code of the k = 1 entry points, instruction for
 // instruction; KM = MC_TATTN_KMAX serves 1 <= K <= KM of the *_topk entries with the K indices / references of a row in
 // registers (loops over j < KM fully unrolled, left at the first j >= K, which is uniform).
+// Region weights (motion mask): template flag W of the loss read-out and of the backward.  W = false is the code of the
+// unweighted entry points (no pointer test in them); W = true reads one weight per query row, row_w[(b, pixel)][f], next to the
+// row's reference values and multiplies the row's squared errors / seeds with it.  The products are arranged so that a weight of
+// 1.0f changes no rounding step: weights of ones give the unweighted entries' bits.
 #include "mc_common.hpp"
 #include <cstdlib>
 
@@ -170,11 +174,12 @@ __device__ __forceinline__ void t_softmax_T(f32x4 (&st)[NT], float& m, float& l)
 // mode 2: write the per-query squared error (P[q, idx[q]] - ref[q])^2 summed per unit.
 // KM > 1 (modes 1 and 2 only): K = Krt values / indices per query, [.., F, K] - mode 1 the K largest fp16 probabilities in
 // descending order, equal ones by ascending frame; mode 2 the squared errors of all K entries of a row.
-template <int NT, int DT, int KM = 1>
+// W (mode 2 only): the squared errors of query frame f are weighted by row_w[(b * HW + p) * F + f].
+template <int NT, int DT, int KM = 1, bool W = false>
 __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, int ldo, int mode,
                                                          half_t* top_val, uint8_t* top_idx,
                                                          const uint8_t* ref_idx, const float* ref_val,
-                                                         float* unit_loss, int Krt) {
+                                                         float* unit_loss, int Krt, const float* row_w) {
     const int K = KM == 1 ? 1 : Krt;
     const int lane = threadIdx.x & 63;
     TUnit u = t_unit(P);
@@ -299,6 +304,8 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
         t_softmax_T<NT>(st, m, l);
         const float inv = 1.0f / l;
         if (mode == 2) {
+            float wq = 1.f;
+            if constexpr (W) wq = lane < 16 && qf < P.F ? row_w[((size_t)u.b * P.HW + u.p) * P.F + qf] : 0.f;
 #pragma unroll
             for (int j = 0; j < KM; ++j) {
                 if (j >= K) break;   // uniform
@@ -312,7 +319,13 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
                 pv = group_sum(pv);
                 if (lane < 16 && qf < P.F) {
                     float dlt = pv - ref_val[(unit * P.F + qf) * K + j];
-                    loss_acc += dlt * dlt;
+                    if constexpr (W) {
+                        // (w dlt) dlt with the first product kept a value of its own: w (dlt dlt) fused into the sum would
+                        // round dlt^2 once more than the unweighted dlt * dlt + acc does, also at w = 1
+                        loss_acc += opaque(wq * dlt) * dlt;
+                    } else {
+                        loss_acc += dlt * dlt;
+                    }
                 }
             }
             continue;
@@ -427,11 +440,13 @@ __global__ __launch_bounds__(256) void tattn_fwd_vec_kernel(TParams P, half_t* o
 // ds_read_b64_tr_b16 - 8 load instructions per unit at d = 40 instead of 48 (36 of them two-byte gathers).
 // KM > 1: K = Krt seeds per query row, ref_idx / ref_val [.., F, K]; the seeds of a row ACCUMULATE in the order of j, so a
 // row that names one frame twice gets both contributions (what gather + autograd gives).
-template <int NT, int DT, int VAR = 0, bool VEC = false, int KM = 1>
+// W: the seeds of query row f are scaled by row_w[(b * HW + p) * F + f] (ref_idx / ref_val / row_w all non-null then):
+// the row's coefficient seed_coef * w is formed once, where the row's references are loaded.
+template <int NT, int DT, int VAR = 0, bool VEC = false, int KM = 1, bool W = false>
 __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t* dO, int lddo, half_t* dq,
                                                          half_t* dk, half_t* dv, int ldg,
                                                          const uint8_t* ref_idx, const float* ref_val,
-                                                         float seed_coef, float* dbg, int Krt) {
+                                                         float seed_coef, float* dbg, int Krt, const float* row_w) {
     const int K = KM == 1 ? 1 : Krt;
     constexpr int NS = (DT + 1) / 2;
     constexpr int PB = 64 * NS + 16;            // VEC: image row pitch, bytes
@@ -542,9 +557,11 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
     float mq[NT], lq[NT], Dq[NT];
     int idxq[NT][KM];
     float refq[NT][KM];
+    float cq[NT];   // W: seed coefficient of the lane's query row
 #pragma unroll
     for (int tq = 0; tq < NT; ++tq) {
         const int qv = 16 * tq + c15;
+        if constexpr (W) cq[tq] = qv < P.F ? seed_coef * row_w[((size_t)u.b * P.HW + u.p) * P.F + qv] : 0.f;
 #pragma unroll
         for (int j = 0; j < KM; ++j) {
             const bool on = ref_idx && qv < P.F && j < K;
@@ -581,7 +598,11 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 #pragma unroll
                 for (int j = 0; j < KM; ++j) {
                     if (j >= K) break;   // uniform
-                    if (kv == idxq[tq][j]) d += seed_coef * (pv - refq[tq][j]);
+                    if constexpr (W) {
+                        if (kv == idxq[tq][j]) d += cq[tq] * (pv - refq[tq][j]);
+                    } else {
+                        if (kv == idxq[tq][j]) d += seed_coef * (pv - refq[tq][j]);
+                    }
                 }
 #if MC_TATTN_PROBE & 1   // tools/tattn_race.py: which packed-fp32 chain of an SLP build goes wrong (see header)
                 pv = opaque(pv);
@@ -615,6 +636,8 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
             float m = shfl(mq[tq], src), l = shfl(lq[tq], src), D = shfl(Dq[tq], src);
             int idx[KM];
             float rf[KM];
+            float cr = seed_coef;
+            if constexpr (W) cr = shfl(cq[tq], src);
 #pragma unroll
             for (int j = 0; j < KM; ++j) {
                 if (j >= K) break;   // uniform
@@ -632,7 +655,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 #pragma unroll
                     for (int j = 0; j < KM; ++j) {
                         if (j >= K) break;   // uniform
-                        if (kv == idx[j]) d += seed_coef * (pv - rf[j]);
+                        if (kv == idx[j]) d += cr * (pv - rf[j]);
                     }
                 }
                 pr[tq][tk][i] = (half_t)pv;
@@ -721,12 +744,12 @@ static thread_local int g_tattn_last = 0;   // 1: the calling thread's last temp
 static float* g_tattn_debug_buf = nullptr;   // mc_tattn_debug_buffer: intermediates of the F <= 16, d = 40 backward (tools build only)
 #endif
 
-template <int NT, int DT, int KM = 1>
+template <int NT, int DT, int KM = 1, bool W = false>
 static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t* tv, uint8_t* ti,
-                         const uint8_t* ri, const float* rv, float* ul, hipStream_t s, int K = 1) {
+                         const uint8_t* ri, const float* rv, float* ul, hipStream_t s, int K = 1, const float* rw = nullptr) {
     long units = (long)P.B * P.HW * P.heads;
     g_tattn_last = 0;
-    if constexpr (KM == 1 && (DT == 3 || DT == 5 || DT == 10)) {
+    if constexpr (KM == 1 && !W && (DT == 3 || DT == 5 || DT == 10)) {
         // attention output, rows readable 16 bytes at a time (MC_TATTN_VEC=0: the 8-byte kernel, A/B)
         static const int vec_env = MC_ENV_INT("MC_TATTN_VEC", 1);
         const bool aligned = ((uintptr_t)P.q | (uintptr_t)P.k | (uintptr_t)P.v) % 16 == 0;
@@ -736,19 +759,20 @@ static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t*
             return;
         }
     }
-    MC_LAUNCH((tattn_fwd_kernel<NT, DT, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, o, ldo, mode, tv,
-              ti, ri, rv, ul, K);
+    MC_LAUNCH((tattn_fwd_kernel<NT, DT, KM, W>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, o, ldo, mode, tv,
+              ti, ri, rv, ul, K, rw);
 }
-template <int NT, int DT, int KM = 1>
+template <int NT, int DT, int KM = 1, bool W = false>
 static void t_launch_bwd(const TParams& P, const half_t* dO, int lddo, half_t* dq, half_t* dk, half_t* dv,
-                         int ldg, const uint8_t* ri, const float* rv, float coef, hipStream_t s, int K = 1) {
+                         int ldg, const uint8_t* ri, const float* rv, float coef, hipStream_t s, int K = 1,
+                         const float* rw = nullptr) {
     long units = (long)P.B * P.HW * P.heads;
     g_tattn_last = 0;
 #ifdef MC_TOOLS
-    if constexpr (KM == 1 && NT == 1 && DT == 3) {
+    if constexpr (KM == 1 && !W && NT == 1 && DT == 3) {
         if (g_tattn_debug_buf) {
             MC_LAUNCH((tattn_bwd_kernel<NT, DT, 1>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo,
-                      dq, dk, dv, ldg, ri, rv, coef, g_tattn_debug_buf, 1);
+                      dq, dk, dv, ldg, ri, rv, coef, g_tattn_debug_buf, 1, (const float*)nullptr);
             return;
         }
     }
@@ -760,15 +784,15 @@ static void t_launch_bwd(const TParams& P, const half_t* dO, int lddo, half_t* d
         constexpr size_t smem = (size_t)4 * 3 * 16 * NT * (64 * NS + 16);
         // (images of at most 48 KiB per workgroup: F <= 16 at d = 40 / 80; beyond that the occupancy lost costs more)
         if (smem <= 48 * 1024 && vec_env && P.d % 8 == 0 && P.ld % 8 == 0 && (!dO || lddo % 8 == 0) && aligned) {
-            allow_big_smem(tattn_bwd_kernel<NT, DT, 0, true, KM>, smem);
-            MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, true, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), smem, s, P, dO, lddo,
-                      dq, dk, dv, ldg, ri, rv, coef, (float*)nullptr, K);
+            allow_big_smem(tattn_bwd_kernel<NT, DT, 0, true, KM, W>, smem);
+            MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, true, KM, W>), dim3((unsigned)((units + 3) / 4)), dim3(256), smem, s, P, dO, lddo,
+                      dq, dk, dv, ldg, ri, rv, coef, (float*)nullptr, K, rw);
             g_tattn_last = 1;
             return;
         }
     }
-    MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, false, KM>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo, dq, dk,
-              dv, ldg, ri, rv, coef, (float*)nullptr, K);
+    MC_LAUNCH((tattn_bwd_kernel<NT, DT, 0, false, KM, W>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, dO, lddo, dq, dk,
+              dv, ldg, ri, rv, coef, (float*)nullptr, K, rw);
 }
 
 #define MC_T_DISPATCH(CALL)                                                     \
@@ -930,6 +954,52 @@ extern "C" int mc_tattn_bwd_topk_f16(const void* q, const void* k, const void* v
 #define CALL(NT_, DT_)                                                                                               \
     t_launch_bwd<NT_, DT_, MC_TATTN_KMAX>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,  \
                                           (const uint8_t*)ref_idx, ref_val, seed_coef, s, K)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// Region-weighted loss: the squared errors of query frame f at (b, pixel) times row_w[(b * HW + p) * F + f], over the UNWEIGHTED
+// element count.  K = 1 runs the KM = 1 instantiation and K > 1 the KM = MC_TATTN_KMAX one, as the unweighted entries do.
+extern "C" int mc_tattn_loss_weighted_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val,
+                                          int K, const float* row_w, float* unit_loss, float* loss, int B, int F, int HW,
+                                          int heads, int d, float scale, void* stream) {
+    TParams P = t_params(q, k, k, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_k(P, K) || !row_w) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                    \
+    if (K == 1)                                                                                                           \
+        t_launch_fwd<NT_, DT_, 1, true>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, unit_loss, s, 1, \
+                                        row_w);                                                                           \
+    else                                                                                                                  \
+        t_launch_fwd<NT_, DT_, MC_TATTN_KMAX, true>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, \
+                                                    unit_loss, s, K, row_w)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    long units = (long)B * HW * heads;
+    MC_LAUNCH(reduce_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)unit_loss, units,
+              1.0f / (float)(units * F * K), loss);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// mc_tattn_bwd_f16 / mc_tattn_bwd_topk_f16 with the seeds of query row f scaled by row_w[(b * HW + p) * F + f]
+extern "C" int mc_tattn_bwd_weighted_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo,
+                                         void* dq, void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val,
+                                         int K, const float* row_w, float seed_coef, int B, int F, int HW, int heads, int d,
+                                         float scale, void* stream) {
+    TParams P = t_params(q, k, v, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_k(P, K) || ldg % 4 || (dO && lddo % 4)) return MC_ERR_SHAPE;
+    if (!ref_idx || !ref_val || !row_w) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                     \
+    if (K == 1)                                                                                                            \
+        t_launch_bwd<NT_, DT_, 1, true>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,          \
+                                        (const uint8_t*)ref_idx, ref_val, seed_coef, s, 1, row_w);                         \
+    else                                                                                                                   \
+        t_launch_bwd<NT_, DT_, MC_TATTN_KMAX, true>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg, \
+                                                    (const uint8_t*)ref_idx, ref_val, seed_coef, s, K, row_w)
     MC_T_DISPATCH(CALL)
 #undef CALL
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;

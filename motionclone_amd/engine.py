@@ -30,8 +30,49 @@ MAX_TOPK = 8     # largest sparsity k of a motion representation (csrc/temporal.
 
 
 def representation_k(rep_dev):
-    """the top-k sparsity K of a prepared representation {name: (idx [BN, heads, F, K], val)}"""
+    """the top-k sparsity K of a prepared representation {name: (idx [BN, heads, F, K], val[, row weights])}"""
     return next(iter(rep_dev.values()))[0].shape[-1] if rep_dev else 1
+
+
+MASK_SCALES = (1, 2, 4, 8)    # latent grid / grid of a hooked temporal attention
+
+
+def check_motion_mask(mask, frames, grid):
+    """A motion mask - where in the picture the reference motion is cloned - as a float64 CPU tensor [F, H', W'].
+    Accepted: a non-negative, finite tensor [H', W'] (every frame) or [F, H', W'] with H', W' integer multiples (1 included)
+    of the latent grid `grid` = (H, W); anything else is a ValueError naming what is wrong."""
+    if not isinstance(mask, torch.Tensor):
+        mask = torch.as_tensor(mask)
+    if mask.dim() not in (2, 3):
+        raise ValueError("motion mask: %d dimensions %s, expected [H', W'] or [F, H', W']" % (mask.dim(), tuple(mask.shape)))
+    H, W = int(grid[0]), int(grid[1])
+    m = mask.detach().to("cpu", torch.float64)
+    if m.dim() == 3 and m.shape[0] != int(frames):
+        raise ValueError("motion mask: shape %s holds %d frames, the run has %d" % (tuple(m.shape), m.shape[0], int(frames)))
+    mh, mw = int(m.shape[-2]), int(m.shape[-1])
+    if mh < H or mw < W or mh % H or mw % W:
+        raise ValueError("motion mask: grid %d x %d is not an integer multiple of the latent grid %d x %d" % (mh, mw, H, W))
+    if not bool(torch.isfinite(m).all()):
+        raise ValueError("motion mask: holds NaN or infinite values")
+    if bool((m < 0).any()):
+        raise ValueError("motion mask: holds negative values (minimum %g)" % float(m.min()))
+    if m.dim() == 2:
+        m = m.unsqueeze(0).expand(int(frames), -1, -1)
+    return m
+
+
+def reduce_motion_mask(mask64, grid, hw):
+    """row weights [hw, F] (float64) of a hooked attention with `hw` positions per frame: the area mean of the checked mask
+    [F, H', W'] over the block of the picture that each position covers (position order (y, x), as the BN axis)"""
+    H, W = int(grid[0]), int(grid[1])
+    s = math.isqrt(max(1, (H * W) // max(1, hw)))
+    if s not in MASK_SCALES or s * s * hw != H * W or H % s or W % s:
+        raise ValueError("motion mask: a hooked attention with %d positions per frame is no 1 / %s reduction of the latent "
+                         "grid %d x %d" % (hw, list(MASK_SCALES), H, W))
+    F_, mh, mw = mask64.shape
+    kh, kw = mh // (H // s), mw // (W // s)
+    pooled = mask64.reshape(F_, H // s, kh, W // s, kw).sum((2, 4)) / float(kh * kw)
+    return pooled.reshape(F_, hw).t().contiguous()
 
 
 def default_config():
@@ -511,7 +552,7 @@ class UNet3DEngine:
     def _motion(self, name, x, geo, tape, record, seeds):
         """VanillaTemporalModule (motion_module.py:80-85,137-161,213-225,274-345).
         record: dict collecting the fused q|k|v buffer of hooked attentions (MySelfAttnProcessor.record_qkv);
-        seeds: {attention name: (ref_idx u8, ref_val f32, coef)} guidance seeds for the backward."""
+        seeds: {attention name: (ref_idx u8, ref_val f32, coef[, row weights f32 [BN, F] or None])} guidance seeds for the backward."""
         w, cfg = self.w, self.cfg
         heads = cfg["motion_heads"]
         C = x.shape[1]
@@ -571,7 +612,7 @@ class UNet3DEngine:
                 ops.tattn_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], da, dqkv[:, :C], dqkv[:, C:2 * C],
                               dqkv[:, 2 * C:], g1.B, g1.F, hw1, heads, d,
                               ref_idx=seed[0] if seed else None, ref_val=seed[1] if seed else None,
-                              seed_coef=seed[2] if seed else 0.0)
+                              seed_coef=seed[2] if seed else 0.0, row_w=seed[3] if seed and len(seed) > 3 else None)
                 dn = ops.gemm(dqkv, w.cat_lin_t([ap + "to_q.weight", ap + "to_k.weight", ap + "to_v.weight"]))
                 dh = ops.layernorm_bwd(dn, hin, ls, w.vec(b + "norms.%d.weight" % a), add=dh)
             dhn = ops.gemm(dh, w.lin_t(p + "proj_in.weight"))
@@ -783,23 +824,50 @@ class UNet3DEngine:
                     for v in range(V)]
         return rep
 
-    def prepare_representation(self, rep, frames=None):
+    def prepare_representation(self, rep, frames=None, mask=None, mask_normalize=False, grid=None):
         """reference .pt dict {name: [values [BN, heads, F, K], indices uint8]} -> device tensors for the kernels; K is the
         sparsity of the representation (1 in the reference's own files, 1 <= K <= min(F, 8) here), one K for all entries.
         A LIST of such dicts (V videos batched in one forward, guided_eps_and_grad) is concatenated along the (b, pixel) axis
         in video order - the order of the conditional halves [c_1 .. c_V] in the batch; the V videos share one K.
         Every entry is validated (ValueError naming the module and the shape): the kernels index [.., F, K] with the K they
         are told, so a file of another layout would otherwise be read with the wrong stride without any error.
-        `frames`: the video length F of the run, where the caller knows it."""
+        `frames`: the video length F of the run, where the caller knows it.
+        `mask`: a motion mask (check_motion_mask; `grid` = the latent grid (H, W) of the run is then required), for a list of
+        representations a list of masks with None entries allowed (one tensor: the same mask for every video).  Every entry
+        then carries a third element, the fp32 row weights [BN, F] of that module - the mask's area mean over the block each
+        position covers, reduced HERE, once per video (the steps only read them); videos of a packed batch without a mask
+        get ones.  `mask_normalize`: the weights of each video and module are divided by their mean (ValueError where that
+        is 0).  With no mask anywhere the entries stay two-tuples and nothing downstream changes."""
         if isinstance(rep, (list, tuple)):
-            parts = [self.prepare_representation(r, frames) for r in rep]
+            V = len(rep)
+            if isinstance(mask, (list, tuple)):
+                if len(mask) != V:
+                    raise ValueError("motion mask: a list of %d masks for %d motion representations" % (len(mask), V))
+                masks = list(mask)
+            else:
+                masks = [mask] * V
+            parts = [self.prepare_representation(r, frames, m, mask_normalize, grid) for r, m in zip(rep, masks)]
             if len(parts) == 1:
                 return parts[0]
             ks = [representation_k(p) for p in parts]
             if len(set(ks)) != 1:
                 raise ValueError("the motion representations of one packed batch differ in their top-k: %s" % ks)
-            return {name: (torch.cat([p[name][0] for p in parts], 0).contiguous(), torch.cat([p[name][1] for p in parts], 0).contiguous())
-                    for name in parts[0]}
+            out = {}
+            for name in parts[0]:
+                ent = [torch.cat([p[name][0] for p in parts], 0).contiguous(), torch.cat([p[name][1] for p in parts], 0).contiguous()]
+                if any(len(p[name]) == 3 for p in parts):
+                    ent.append(torch.cat([p[name][2] if len(p[name]) == 3 else
+                                          torch.ones((p[name][0].shape[0], p[name][0].shape[2]), dtype=torch.float32, device=self.dev)
+                                          for p in parts], 0).contiguous())
+                out[name] = tuple(ent)
+            return out
+        mask64 = None
+        if mask is not None:
+            if grid is None:
+                raise ValueError("motion mask: the latent grid (H, W) of the run is needed to place the mask (grid=...)")
+            if frames is None:
+                frames = next(iter(rep.values()))[0].shape[2] if len(rep) else 0
+            mask64 = check_motion_mask(mask, frames, grid)
         out = {}
         for name, (val, idx) in rep.items():
             vs, is_ = tuple(val.shape), tuple(idx.shape)
@@ -813,10 +881,18 @@ class UNet3DEngine:
             if frames is not None and vs[2] != int(frames):
                 raise ValueError("motion representation %s: shape %s holds %d frames, the run has %d" % (name, vs, vs[2], int(frames)))
             out[name] = (idx.to(self.dev, torch.uint8).contiguous(), val.to(self.dev, torch.float32).contiguous())
-        ks = sorted({i.shape[3] for i, _ in out.values()})
+            if mask64 is not None:
+                w = reduce_motion_mask(mask64, grid, vs[0])
+                if mask_normalize:
+                    mean = float(w.mean())
+                    if mean == 0.0:
+                        raise ValueError("motion mask: motion_mask_normalize with a mask whose mean over %s is 0" % name)
+                    w = w / mean
+                out[name] = out[name] + (w.to(self.dev, torch.float32).contiguous(),)
+        ks = sorted({e[0].shape[3] for e in out.values()})
         if len(ks) > 1:
             raise ValueError("the entries of one motion representation differ in their top-k: %s"
-                             % {n: tuple(i.shape) for n, (i, _) in out.items()})
+                             % {n: tuple(e[0].shape) for n, e in out.items()})
         return out
 
     @ops.scoped
@@ -847,15 +923,20 @@ class UNet3DEngine:
         # of a row's K seeds is 1 / K of the k = 1 seed: the gradient per ROW stays in the range validated for k = 1.  The scale
         # therefore follows the number of rows (numel / K); following numel would multiply by K on top of that and spend fp16
         # headroom for nothing.
-        for name, (idx, _) in rep_dev.items():
+        for name, ent in rep_dev.items():
+            idx = ent[0]
             if idx.dim() != 4 or idx.shape[2] != latents.shape[2]:
                 raise ValueError("motion representation %s: shape %s for a run of %d frames" % (name, tuple(idx.shape), latents.shape[2]))
-        numel_max = max((idx.numel() // idx.shape[-1] // V for idx, _ in rep_dev.values()), default=1)
+        numel_max = max((ent[0].numel() // ent[0].shape[-1] // V for ent in rep_dev.values()), default=1)
         tape.grad_scale = self.grad_scale * float(2 ** max(0, round(math.log2(max(1.0, numel_max / 32768.0)))))
         seeds = {}
-        for name, (idx, val) in rep_dev.items():
+        # A motion mask (third element of an entry: row weights [BN, F], normalisation already folded in by
+        # prepare_representation) scales the seed of each query row inside the kernel; the coefficient keeps the unmasked
+        # denominator, and grad_scale does not look at the weights.
+        for name, ent in rep_dev.items():
+            idx, val = ent[0], ent[1]
             numel = idx.numel() // V              # per video: F.mse_loss averages over ONE video's map (all K entries per row)
-            seeds[name] = (idx, val, tape.grad_scale * float(weight) * 2.0 / numel)
+            seeds[name] = (idx, val, tape.grad_scale * float(weight) * 2.0 / numel, ent[2] if len(ent) == 3 else None)
         record = {}
         if batched:
             text2 = torch.cat([text_uncond, text_cond], 0)
@@ -874,10 +955,11 @@ class UNet3DEngine:
         loss = None
         if want_loss:
             total = None
-            for name, (idx, val) in rep_dev.items():
+            for name, ent in rep_dev.items():
                 r = record[name]
                 C, g = r["C"], r["geo"]
-                lm = ops.tattn_loss(r["qkv"][:, :C], r["qkv"][:, C:2 * C], idx, val, g.B, g.F, g.hw, r["heads"], r["d"])
+                lm = ops.tattn_loss(r["qkv"][:, :C], r["qkv"][:, C:2 * C], ent[0], ent[1], g.B, g.F, g.hw, r["heads"], r["d"],
+                                    row_w=ent[2] if len(ent) == 3 else None)
                 total = lm if total is None else total + lm
             loss = total * (float(weight) * V)   # tattn_loss is the mean over all V maps; the sum of the V means is V x that
         tape.latent_grad = None

@@ -540,13 +540,29 @@ def tattn_prob(q, k, B, F, HW, heads, d, scale=None):
     return prob
 
 
-def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None):
-    """mean((gather(P, ref_idx) - ref_val)^2) over all entries; the sparsity K is ref_idx.shape[-1]"""
+def _row_w(row_w, BN, F):
+    """region weights of the guidance (motion mask): fp32, contiguous, [BN, F] - one per (b, pixel) and query frame"""
+    if row_w.dtype != torch.float32:
+        raise ValueError("row_w must be float32, got %s" % row_w.dtype)
+    if not row_w.is_contiguous():
+        raise ValueError("row_w must be contiguous")
+    if tuple(row_w.shape) != (BN, F):
+        raise ValueError("row_w %s for [BN = %d, F = %d]" % (tuple(row_w.shape), BN, F))
+    return row_w
+
+
+def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None, row_w=None):
+    """mean((gather(P, ref_idx) - ref_val)^2) over all entries; the sparsity K is ref_idx.shape[-1].
+    `row_w` [BN, F]: every squared error of query frame f at (b, pixel) is weighted by row_w[bn, f]; the mean keeps the
+    unweighted denominator.  None: the unweighted entries."""
     scale = d ** -0.5 if scale is None else scale
     K = _seed_k(ref_idx, ref_val, B * HW, heads, F)
     ul = workspace("tattn_loss", q, B, HW, heads)
     loss = empty((1,), q, torch.float32)
-    if K == 1:
+    if row_w is not None:
+        lib.call("mc_tattn_loss_weighted_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), K, _p(_row_w(row_w, B * HW, F)),
+                 _p(ul), _p(loss), B, F, HW, heads, d, float(scale), _stream(q))
+    elif K == 1:
         lib.call("mc_tattn_loss_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), _p(ul), _p(loss), B, F, HW,
                  heads, d, float(scale), _stream(q))
     else:
@@ -556,10 +572,18 @@ def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None):
 
 
 def tattn_bwd(q, k, v, do, dq, dk, dv, B, F, HW, heads, d, ref_idx=None, ref_val=None, seed_coef=0.0,
-              scale=None):
+              scale=None, row_w=None):
+    """`row_w` [BN, F] (needs the seed): the seed of query frame f at (b, pixel) is scaled by row_w[bn, f]"""
     scale = d ** -0.5 if scale is None else scale
     assert _ld(q) == _ld(k) == _ld(v) and _ld(dq) == _ld(dk) == _ld(dv)
     K = 1 if ref_idx is None else _seed_k(ref_idx, ref_val, B * HW, heads, F)
+    if row_w is not None:
+        if ref_idx is None:
+            raise ValueError("row_w weights the guidance seed: ref_idx / ref_val are required")
+        lib.call("mc_tattn_bwd_weighted_f16", _p(q), _p(k), _p(v), _ld(q), _p(do), _ld(do), _p(dq), _p(dk), _p(dv), _ld(dq),
+                 _p(ref_idx), _p(ref_val), K, _p(_row_w(row_w, B * HW, F)), float(seed_coef), B, F, HW, heads, d,
+                 float(scale), _stream(q))
+        return
     if K != 1:
         lib.call("mc_tattn_bwd_topk_f16", _p(q), _p(k), _p(v), _ld(q), _p(do), _ld(do), _p(dq), _p(dk), _p(dv), _ld(dq),
                  _p(ref_idx), _p(ref_val), K, float(seed_coef), B, F, HW, heads, d, float(scale), _stream(q))

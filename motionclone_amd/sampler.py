@@ -131,10 +131,12 @@ class MotionCloneSampler:
 
     def _graphed_step(self, latents, i, text, rep_dev, ctrl):
         """One hipGraph per (step index, shapes).  Everything that changes between videos - latents, text embeddings, the
-        motion representation, the SparseCtrl condition - enters through static buffers that are refreshed by copies before
+        motion representation with its region weights (a new mask of the same shape is a copy, not a capture), the SparseCtrl
+        condition - enters through static buffers that are refreshed by copies before
         the replay, so a graph captured on the first video serves every later (prompt, reference-video) pair."""
         guided = i < self.G
-        rsig = tuple((k, tuple(v[0].shape)) for k, v in rep_dev.items()) if guided else ()
+        # (name, shape, weighted?): a motion mask adds the row weights as a third static buffer and runs other kernels
+        rsig = tuple((k, tuple(v[0].shape), len(v) == 3) for k, v in rep_dev.items()) if guided else ()
         csig = None if ctrl is None else (tuple(ctrl["cond"].shape), tuple(ctrl["mask"].shape), float(ctrl.get("scale", 1.0)))
         key = (i, tuple(latents.shape), tuple(text.shape), rsig, csig, self._gemm_share())   # the GEMM geometry is baked in
         ent = self._graphs.get(key)
@@ -215,7 +217,8 @@ class MotionCloneSampler:
     @ops.scoped
     def _step_eager(self, latents, i, text, rep_dev, aux=None, ctrl=None, sigma=0.0):
         """latents [V, 4, F, H, W]; text [2 V, n, dim] ordered [u_1 .. u_V | c_1 .. c_V] (V = 1: [uncond, cond], the reference's
-        layout); rep_dev: engine.prepare_representation of the V representations (a list for V > 1).  V > 1 = V independent
+        layout); rep_dev: engine.prepare_representation of the V representations (a list for V > 1), its entries two-tuples or,
+        with a motion mask, three-tuples whose last element is the row weights [BN, F].  V > 1 = V independent
         videos through ONE launch sequence (same kernels, V times the rows): each video's arithmetic is its own - no
         reduction crosses the batch - but the GEMM tile / split-K choice follows the larger row count, so results agree
         with the one-video path to fp16 rounding, not bit for bit.  ctrl: `cond` [V, ...] / `mask` [V, 1, ...] carry one
@@ -264,8 +267,10 @@ class MotionCloneSampler:
             aux.update(eps_u=eps2[:T1], eps_c=eps2[T1:])
         return update(eps2[T1:], eps2[:T1], None, 0.0)
 
-    def sample(self, latents, text, rep, progress=None, ctrl=None):
-        rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2])
+    def sample(self, latents, text, rep, progress=None, ctrl=None, mask=None, mask_normalize=False):
+        """`mask`: a motion mask (a list with None entries for V > 1), see engine.prepare_representation"""
+        rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2], mask=mask, mask_normalize=mask_normalize,
+                                                     grid=tuple(latents.shape[3:]))
         for i in range(len(self.timesteps)):
             latents = self.step(latents, i, text, rep_dev, ctrl=ctrl)
             if progress is not None:

@@ -90,6 +90,33 @@ def _motion_topk(cfg, override=None):
     return 1 if k is None else int(k)
 
 
+def _load_mask(m):
+    """a motion mask given as a tensor / array or as the path of a `.pt` (torch.save of the tensor) or `.npy` file"""
+    if m is None or isinstance(m, torch.Tensor):
+        return m
+    if isinstance(m, (str, os.PathLike)):
+        path = os.fspath(m)
+        if path.endswith(".npy"):
+            return torch.from_numpy(np.load(path))
+        if path.endswith(".pt"):
+            return torch.as_tensor(torch.load(path, map_location="cpu"))
+        raise ValueError("motion mask file %s: expected a .pt or .npy file" % path)
+    return torch.as_tensor(m)
+
+
+def _motion_mask(pipe, override=None):
+    """the motion mask of the next sampling run (where the reference motion is cloned; engine.check_motion_mask): a per-call /
+    per-example override (tensor or path), else the pipeline attribute `motion_mask`, else the optional inference-yaml key
+    `motion_mask_path`; None = no mask, every path as without the feature.  -> (tensor or None, motion_mask_normalize)"""
+    cfg = pipe.input_config
+    m = override
+    if m is None:
+        m = getattr(pipe, "motion_mask", None)
+    if m is None:
+        m = getattr(cfg, "motion_mask_path", None)
+    return _load_mask(m), bool(getattr(cfg, "motion_mask_normalize", False) or False)
+
+
 @torch.no_grad()
 def obtain_motion_representation(self, generator=None, motion_representation_path: str = None, duration=None,
                                  use_controlnet=False, video_latents=None, uncond_embeddings=None, video_data=None,
@@ -203,9 +230,19 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
         cond[:, :, self.input_config.image_index] = ci
         mask[:, :, self.input_config.image_index] = 1
         ctrl = dict(cond=cond, mask=mask, scale=self.input_config.controlnet_scale)
-    if getattr(self, "_mc_rep_src", None) is not self.motion_representation_dict:
-        self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2])
+    if not hasattr(self, "_mc_mask"):            # called without sample_video: the configured mask, read once
+        self._mc_mask = _motion_mask(self)
+    mask, mask_norm = self._mc_mask
+    if (getattr(self, "_mc_rep_src", None) is not self.motion_representation_dict
+            or getattr(self, "_mc_rep_mask", None) is not self._mc_mask):
+        if mask is None:
+            self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2])
+        else:                                    # reduced to the hooked modules' grids here, once per video
+            self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2],
+                                                                 mask=mask, mask_normalize=mask_norm,
+                                                                 grid=tuple(noisy_latents.shape[3:]))
         self._mc_rep_src = self.motion_representation_dict
+        self._mc_rep_mask = self._mc_mask
     kw = dict(extra_step_kwargs or {})      # prepare_extra_step_kwargs: eta / generator, handed to customized_step (:241,255)
     out = smp.step(noisy_latents.half(), step_index, self.text_embeddings.half(), self._mc_rep_dev, ctrl=ctrl,
                    eta=float(kw.get("eta", 0.0) or 0.0), generator=kw.get("generator") if kw.get("eta") else None)
@@ -217,10 +254,12 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
 
 
 def sample_video(self, eta: float = 0.0, generator=None, noisy_latents: Optional[torch.Tensor] = None,
-                 add_controlnet: bool = False, text_embeddings=None, decode=True, controlnet_images=None):
-    """:102-171"""
+                 add_controlnet: bool = False, text_embeddings=None, decode=True, controlnet_images=None, motion_mask=None):
+    """:102-171.  `motion_mask` (tensor or path; default: the pipeline attribute `motion_mask`, then the yaml key
+    `motion_mask_path`): region weights of the guidance for this video."""
     self.add_controlnet = add_controlnet
     cfg = self.input_config
+    self._mc_mask = _motion_mask(self, motion_mask)
     if add_controlnet and controlnet_images is not None:
         # already what the ControlNet consumes (:122-128): VAE latents [1, 4, n, h, w], or pixels in [0, 1] [1, 3, n, H, W]
         self.controlnet_images = controlnet_images
@@ -297,11 +336,12 @@ _MIXED = "either every example carries a condition image or none does"
 
 
 @torch.no_grad()
-def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None):
+def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None, masks=None):
     """The packed step loop on this pipeline's sampler for V videos whose per-example host work is done: `latents` V tensors
     [1, 4, F, H, W], `texts` V [2, n, dim] ([uncond, cond]), `reps` V motion representations, `ctrls` V SparseCtrl dicts
     (cond / mask [1, ...] placed at image_index, scale) or V times None, `generators` the V generators that `eta > 0` draws each
-    video's variance noise from, in list order at every step.  Returns the final latents [V, 4, F, H, W] - after a replayed
+    video's variance noise from, in list order at every step, `masks` V motion masks (tensors or None; None = no mask at all).
+    Returns the final latents [V, 4, F, H, W] - after a replayed
     step the graph's static buffer: callers that keep them copy."""
     from ..sampler import batch_ctrl
     cfg = self.input_config
@@ -314,7 +354,11 @@ def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None):
     if use_ctrl[0]:
         smp.controlnet = self.controlnet.engine()
         ctrl = batch_ctrl(list(ctrls), V)
-    rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2])   # one top-k K for the V videos
+    if masks is None or all(m is None for m in masks):
+        rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2])   # one top-k K for the V videos
+    else:
+        rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2], mask=list(masks),
+                                                    mask_normalize=_motion_mask(self)[1], grid=tuple(latents[0].shape[3:]))
     x = torch.cat(list(latents), 0).half()
     text2 = torch.cat([t[0:1] for t in texts] + [t[1:2] for t in texts], 0).half()
     with self.progress_bar(total=cfg.inference_steps) as progress_bar:
@@ -346,7 +390,8 @@ def _run_group(grp, items):
 
     def run():
         x = _packed_sample(pipe, [it["latents"] for it in items], [it["text"] for it in items], [it["rep"] for it in items],
-                           [it["ctrl"] for it in items], eta=etas.pop(), generators=[it["generator"] for it in items])
+                           [it["ctrl"] for it in items], eta=etas.pop(), generators=[it["generator"] for it in items],
+                           masks=[it.get("mask") for it in items])
         return [x[v:v + 1].clone() for v in range(len(items))]
     if not on_gpu:
         return [(o, None) for o in run()]
@@ -377,7 +422,7 @@ def _group_sample(self, grp, noisy_latents, eta, generator):
         ready = torch.cuda.Event()
         ready.record()
     item = dict(pipe=self, latents=noisy_latents, text=self.text_embeddings, rep=self.motion_representation_dict, ctrl=ctrl,
-                eta=float(eta or 0.0), generator=generator, ready=ready)
+                eta=float(eta or 0.0), generator=generator, ready=ready, mask=self._mc_mask[0])
     out = grp.meet(lanes.slot_index(), item, lambda items: _run_group(grp, items))
     if out is None:
         return None
@@ -395,7 +440,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
     arguments of those two functions: `new_prompt` (+ `negative_prompt`) or `text_embeddings` [2, n, dim]; `video_latents` or
     `video_path` / `video_data` (+ `duration`); `uncond_embeddings` (optional); `noisy_latents` or `generator`; for
     image-to-video `controlnet_images` or `condition_image_path_list` (either one turns SparseCtrl on; all examples or none);
-    `motion_topk` overrides input_config.motion_topk for that example (one value for all the examples of a batch).
+    `motion_topk` overrides input_config.motion_topk for that example (one value for all the examples of a batch);
+    `motion_mask` (tensor or path) is that example's motion mask (default: the pipeline's / the yaml's `motion_mask_path`).
     Returns a list of V results, each what `sample_video(decode=...)` returns for that example.
 
     Host work (VAE posterior draw, extraction noise, condition-image VAE draw, CLIP, latent prior) runs per example in list
@@ -423,7 +469,7 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
                                               video_data=ex.get("video_data"), motion_topk=ex.get("motion_topk"))
             return [self.sample_video(eta=eta, generator=ex.get("generator"), noisy_latents=ex.get("noisy_latents"),
                                       add_controlnet=use_ctrl, text_embeddings=ex.get("text_embeddings"), decode=decode,
-                                      controlnet_images=ex.get("controlnet_images"))]
+                                      controlnet_images=ex.get("controlnet_images"), motion_mask=ex.get("motion_mask"))]
         finally:
             for k, v in old.items():
                 setattr(cfg, k, v)
@@ -479,7 +525,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
         ctrls = [dict(cond=c, mask=m, scale=cfg.controlnet_scale) for c, m in zip(smp_c, smp_m)]
     reps = smp.extract(torch.cat(vids, 0).half(), torch.cat(noises, 0).half(), torch.cat(unconds, 0).half(),
                        add_noise_step=step_t, ctrl=ext_ctrl, topk=topks[0])
-    x = _packed_sample(self, lats, texts, reps, ctrls, eta=eta, generators=[ex.get("generator") for ex in examples])
+    x = _packed_sample(self, lats, texts, reps, ctrls, eta=eta, generators=[ex.get("generator") for ex in examples],
+                       masks=[_motion_mask(self, ex.get("motion_mask"))[0] for ex in examples])
     if not decode:
         return [x[v:v + 1].clone() for v in range(V)]     # (a replayed step hands out the graph's static buffer: copies)
     return [self.decode_latents(x[v:v + 1]) for v in range(V)]
