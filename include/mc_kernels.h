@@ -250,6 +250,22 @@ int mc_tattn_bwd_weighted_f16(const void* q, const void* k, const void* v, int l
                               void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, int K,
                               const float* row_w, float seed_coef, int B, int F, int HW, int heads, int d, float scale,
                               void* stream);
+/* motion composition - several references guide one video: the slots of a query row are the references' entries concatenated
+ * along the last axis in reference order, ref_idx u8 / ref_val f32 [B*HW, heads, F, K] with K = sum K_r, 1 <= K <= 8 (NOT
+ * bound by F: two references may name one frame), and slot_w f32 [B*HW, F, K] holds lambda_r * w_r[bn, f] / K_r for a slot
+ * of reference r (heads share it; key frames are not weighted).  A NULL ref_idx / ref_val / slot_w or another K:
+ * MC_ERR_SHAPE, nothing launched.
+ * loss[0] = 1 / (B*HW*heads*F) * sum slot_w[bn, f, s] * (P[q, idx[q][s]] - ref[q][s])^2 - no K in the denominator, it lives
+ * in the weights; a slot of weight 0 adds an exact zero */
+int mc_tattn_loss_slotw_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val, int K,
+                            const float* slot_w, float* unit_loss, float* loss, int B, int F, int HW, int heads, int d,
+                            float scale, void* stream);
+/* dP[q, idx[q][s]] += seed_coef * slot_w[bn, q, s] * (P[q, idx[q][s]] - ref[q][s]) for every s < K; a frame named in two
+ * slots gets both seeds; dO may be NULL */
+int mc_tattn_bwd_slotw_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo, void* dq,
+                           void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val, int K,
+                           const float* slot_w, float seed_coef, int B, int F, int HW, int heads, int d, float scale,
+                           void* stream);
 int mc_reduce_sum_f32(const float* in, long n, float scale, float* out, void* stream);
 
 /* ---- element-wise glue ------------------------------------------------------------------------ */

@@ -23,6 +23,11 @@
 // unweighted entry points (no pointer test in them); W = true reads one weight per query row, row_w[(b, pixel)][f], next to the
 // row's reference values and multiplies the row's squared errors / seeds with it.  The products are arranged so that a weight of
 // 1.0f changes no rounding step: weights of ones give the unweighted entries' bits.
+// Motion composition (several references per video): W = 2 reads one weight per SLOT, slot_w[(b, pixel)][f][s] for s < K, next
+// to the row's K indices / references - the entries of the references concatenated along the last axis, each reference's
+// lambda * mask weight / K_r folded into its slots on the host.  K is then any 1 .. MC_TATTN_KMAX, also beyond F: two
+// references may name one frame, and such a frame gets both seeds.  A slot of weight 0 adds an exact zero.  The backward keeps
+// the K one-byte indices of a row packed four to a register (2 registers and 2 lane broadcasts per row instead of K).
 #include "mc_common.hpp"
 #include <cstdlib>
 
@@ -169,13 +174,55 @@ __device__ __forceinline__ void t_softmax_T(f32x4 (&st)[NT], float& m, float& l)
     l = group_sum(l);
 }
 
+// W = 2: the K slot weights of one query row, w = slot_w + row * K.  Rows of 4 or 8 floats in a 16-byte aligned tensor (vec,
+// uniform) are one or two 16-byte reads, any other K is read slot by slot; slots at / beyond K and rows that are off read as 0.
+template <int KM>
+__device__ __forceinline__ void t_slot_w(const float* w, int K, bool on, bool vec, float (&out)[KM]) {
+    static_assert(KM == 8, "slot weights ride on the KM = MC_TATTN_KMAX instantiations");
+#pragma unroll
+    for (int j = 0; j < KM; ++j) out[j] = 0.f;
+    if (!on) return;
+    if (vec) {
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = lo[j];
+        if (K == 8) {   // uniform
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(w + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[4 + j] = hi[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < KM; ++j)
+            if (j < K) out[j] = w[j];
+    }
+}
+__device__ __forceinline__ bool t_slot_vec(const float* slot_w, int K) { return K % 4 == 0 && (uintptr_t)slot_w % 16 == 0; }
+// W = 2: the K one-byte indices of one query row packed four to a register (slot s: byte s & 3 of word s >> 2), idx = ref_idx +
+// row * K; rows of 4 or 8 indices in a 4-byte aligned tensor (vec, uniform) are one or two 4-byte reads.  Slots at / beyond K and
+// rows that are off hold 0xff, which is no frame (F <= 32).
+__device__ __forceinline__ void t_slot_idx(const uint8_t* idx, int K, bool on, bool vec, unsigned (&out)[2]) {
+    out[0] = out[1] = 0xffffffffu;
+    if (!on) return;
+    if (vec) {
+        out[0] = *reinterpret_cast<const unsigned*>(idx);
+        if (K == 8) out[1] = *reinterpret_cast<const unsigned*>(idx + 4);   // uniform
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < K) out[j >> 2] = (out[j >> 2] & ~(0xffu << (8 * (j & 3)))) | ((unsigned)idx[j] << (8 * (j & 3)));
+    }
+}
+__device__ __forceinline__ int t_slot_of(const unsigned (&pk)[2], int j) { return (int)((pk[j >> 2] >> (8 * (j & 3))) & 0xffu); }
+
 // ---- forward --------------------------------------------------------------------------------
 // mode 0: write attention output o; mode 1: write top-1 (value fp16, index u8) of P per query;
 // mode 2: write the per-query squared error (P[q, idx[q]] - ref[q])^2 summed per unit.
 // KM > 1 (modes 1 and 2 only): K = Krt values / indices per query, [.., F, K] - mode 1 the K largest fp16 probabilities in
 // descending order, equal ones by ascending frame; mode 2 the squared errors of all K entries of a row.
-// W (mode 2 only): the squared errors of query frame f are weighted by row_w[(b * HW + p) * F + f].
-template <int NT, int DT, int KM = 1, bool W = false>
+// W = 1 (mode 2 only): the squared errors of query frame f are weighted by row_w[(b * HW + p) * F + f].
+// W = 2 (mode 2 only): row_w is slot_w [B*HW, F, K]; the squared error of slot s of query frame f is weighted by its own entry.
+template <int NT, int DT, int KM = 1, int W = 0>
 __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, int ldo, int mode,
                                                          half_t* top_val, uint8_t* top_idx,
                                                          const uint8_t* ref_idx, const float* ref_val,
@@ -305,7 +352,11 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
         const float inv = 1.0f / l;
         if (mode == 2) {
             float wq = 1.f;
-            if constexpr (W) wq = lane < 16 && qf < P.F ? row_w[((size_t)u.b * P.HW + u.p) * P.F + qf] : 0.f;
+            if constexpr (W == 1) wq = lane < 16 && qf < P.F ? row_w[((size_t)u.b * P.HW + u.p) * P.F + qf] : 0.f;
+            float ws[W == 2 ? KM : 1];
+            if constexpr (W == 2)
+                t_slot_w<KM>(row_w + (((size_t)u.b * P.HW + u.p) * P.F + (qf < P.F ? qf : 0)) * K, K, lane < 16 && qf < P.F,
+                             t_slot_vec(row_w, K), ws);
 #pragma unroll
             for (int j = 0; j < KM; ++j) {
                 if (j >= K) break;   // uniform
@@ -319,7 +370,9 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TParams P, half_t* o, in
                 pv = group_sum(pv);
                 if (lane < 16 && qf < P.F) {
                     float dlt = pv - ref_val[(unit * P.F + qf) * K + j];
-                    if constexpr (W) {
+                    if constexpr (W == 2) {
+                        loss_acc += opaque(ws[j] * dlt) * dlt;
+                    } else if constexpr (W == 1) {
                         // (w dlt) dlt with the first product kept a value of its own: w (dlt dlt) fused into the sum would
                         // round dlt^2 once more than the unweighted dlt * dlt + acc does, also at w = 1
                         loss_acc += opaque(wq * dlt) * dlt;
@@ -442,7 +495,9 @@ __global__ __launch_bounds__(256) void tattn_fwd_vec_kernel(TParams P, half_t* o
 // row that names one frame twice gets both contributions (what gather + autograd gives).
 // W: the seeds of query row f are scaled by row_w[(b * HW + p) * F + f] (ref_idx / ref_val / row_w all non-null then):
 // the row's coefficient seed_coef * w is formed once, where the row's references are loaded.
-template <int NT, int DT, int VAR = 0, bool VEC = false, int KM = 1, bool W = false>
+// W = 2: row_w is slot_w [B*HW, F, K]; slot s of query row f has its own coefficient seed_coef * slot_w[(b * HW + p)][f][s],
+// formed where the row's references are loaded and carried to the q-row orientation with them.
+template <int NT, int DT, int VAR = 0, bool VEC = false, int KM = 1, int W = 0>
 __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t* dO, int lddo, half_t* dq,
                                                          half_t* dk, half_t* dv, int ldg,
                                                          const uint8_t* ref_idx, const float* ref_val,
@@ -557,15 +612,25 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
     float mq[NT], lq[NT], Dq[NT];
     int idxq[NT][KM];
     float refq[NT][KM];
-    float cq[NT];   // W: seed coefficient of the lane's query row
+    float cq[NT];   // W = 1: seed coefficient of the lane's query row
+    float cs[NT][W == 2 ? KM : 1];   // W = 2: seed coefficients of the row's slots
+    unsigned ipk[NT][2];             // W = 2: the row's indices, four to a register (t_slot_idx)
 #pragma unroll
     for (int tq = 0; tq < NT; ++tq) {
         const int qv = 16 * tq + c15;
-        if constexpr (W) cq[tq] = qv < P.F ? seed_coef * row_w[((size_t)u.b * P.HW + u.p) * P.F + qv] : 0.f;
+        if constexpr (W == 1) cq[tq] = qv < P.F ? seed_coef * row_w[((size_t)u.b * P.HW + u.p) * P.F + qv] : 0.f;
+        if constexpr (W == 2) {
+            t_slot_w<KM>(row_w + (((size_t)u.b * P.HW + u.p) * P.F + (qv < P.F ? qv : 0)) * K, K, qv < P.F, t_slot_vec(row_w, K),
+                         cs[tq]);
+#pragma unroll
+            for (int j = 0; j < KM; ++j) cs[tq][j] *= seed_coef;
+            t_slot_idx(ref_idx + (unit * P.F + (qv < P.F ? qv : 0)) * K, K, qv < P.F, K % 4 == 0 && (uintptr_t)ref_idx % 4 == 0,
+                       ipk[tq]);
+        }
 #pragma unroll
         for (int j = 0; j < KM; ++j) {
             const bool on = ref_idx && qv < P.F && j < K;
-            idxq[tq][j] = on ? (int)ref_idx[(unit * P.F + qv) * K + j] : -1;
+            if constexpr (W != 2) idxq[tq][j] = on ? (int)ref_idx[(unit * P.F + qv) * K + j] : -1;
             refq[tq][j] = on ? ref_val[(unit * P.F + qv) * K + j] : 0.f;
         }
         float m = -INFINITY;
@@ -598,7 +663,9 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 #pragma unroll
                 for (int j = 0; j < KM; ++j) {
                     if (j >= K) break;   // uniform
-                    if constexpr (W) {
+                    if constexpr (W == 2) {
+                        if (kv == t_slot_of(ipk[tq], j)) d += cs[tq][j] * (pv - refq[tq][j]);
+                    } else if constexpr (W == 1) {
                         if (kv == idxq[tq][j]) d += cq[tq] * (pv - refq[tq][j]);
                     } else {
                         if (kv == idxq[tq][j]) d += seed_coef * (pv - refq[tq][j]);
@@ -637,12 +704,19 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
             int idx[KM];
             float rf[KM];
             float cr = seed_coef;
-            if constexpr (W) cr = shfl(cq[tq], src);
+            float crs[W == 2 ? KM : 1];
+            unsigned ipr[2];
+            if constexpr (W == 1) cr = shfl(cq[tq], src);
+            if constexpr (W == 2) {
+                ipr[0] = (unsigned)shfl((int)ipk[tq][0], src);
+                ipr[1] = (unsigned)shfl((int)ipk[tq][1], src);
+            }
 #pragma unroll
             for (int j = 0; j < KM; ++j) {
                 if (j >= K) break;   // uniform
-                idx[j] = shfl(idxq[tq][j], src);
+                if constexpr (W != 2) idx[j] = shfl(idxq[tq][j], src);
                 rf[j] = shfl(refq[tq][j], src);
+                if constexpr (W == 2) crs[j] = shfl(cs[tq][j], src);
             }
             const bool qok = 16 * tq + src < P.F;
 #pragma unroll
@@ -655,7 +729,11 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(TParams P, const half_t*
 #pragma unroll
                     for (int j = 0; j < KM; ++j) {
                         if (j >= K) break;   // uniform
-                        if (kv == idx[j]) d += cr * (pv - rf[j]);
+                        if constexpr (W == 2) {
+                            if (kv == t_slot_of(ipr, j)) d += crs[j] * (pv - rf[j]);
+                        } else {
+                            if (kv == idx[j]) d += cr * (pv - rf[j]);
+                        }
                     }
                 }
                 pr[tq][tk][i] = (half_t)pv;
@@ -744,7 +822,7 @@ static thread_local int g_tattn_last = 0;   // 1: the calling thread's last temp
 static float* g_tattn_debug_buf = nullptr;   // mc_tattn_debug_buffer: intermediates of the F <= 16, d = 40 backward (tools build only)
 #endif
 
-template <int NT, int DT, int KM = 1, bool W = false>
+template <int NT, int DT, int KM = 1, int W = 0>
 static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t* tv, uint8_t* ti,
                          const uint8_t* ri, const float* rv, float* ul, hipStream_t s, int K = 1, const float* rw = nullptr) {
     long units = (long)P.B * P.HW * P.heads;
@@ -762,7 +840,7 @@ static void t_launch_fwd(const TParams& P, half_t* o, int ldo, int mode, half_t*
     MC_LAUNCH((tattn_fwd_kernel<NT, DT, KM, W>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, P, o, ldo, mode, tv,
               ti, ri, rv, ul, K, rw);
 }
-template <int NT, int DT, int KM = 1, bool W = false>
+template <int NT, int DT, int KM = 1, int W = 0>
 static void t_launch_bwd(const TParams& P, const half_t* dO, int lddo, half_t* dq, half_t* dk, half_t* dv,
                          int ldg, const uint8_t* ri, const float* rv, float coef, hipStream_t s, int K = 1,
                          const float* rw = nullptr) {
@@ -818,6 +896,7 @@ static int t_check(const TParams& P) {
     return 1;
 }
 static int t_check_k(const TParams& P, int K) { return K >= 1 && K <= MC_TATTN_KMAX && K <= P.F; }
+static int t_check_slots(int K) { return K >= 1 && K <= MC_TATTN_KMAX; }   // slots of several references: duplicates are legal
 
 }  // namespace mc
 
@@ -970,10 +1049,10 @@ extern "C" int mc_tattn_loss_weighted_f16(const void* q, const void* k, int ld, 
     hipStream_t s = (hipStream_t)stream;
 #define CALL(NT_, DT_)                                                                                                    \
     if (K == 1)                                                                                                           \
-        t_launch_fwd<NT_, DT_, 1, true>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, unit_loss, s, 1, \
+        t_launch_fwd<NT_, DT_, 1, 1>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, unit_loss, s, 1, \
                                         row_w);                                                                           \
     else                                                                                                                  \
-        t_launch_fwd<NT_, DT_, MC_TATTN_KMAX, true>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, \
+        t_launch_fwd<NT_, DT_, MC_TATTN_KMAX, 1>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, \
                                                     unit_loss, s, K, row_w)
     MC_T_DISPATCH(CALL)
 #undef CALL
@@ -995,11 +1074,52 @@ extern "C" int mc_tattn_bwd_weighted_f16(const void* q, const void* k, const voi
     hipStream_t s = (hipStream_t)stream;
 #define CALL(NT_, DT_)                                                                                                     \
     if (K == 1)                                                                                                            \
-        t_launch_bwd<NT_, DT_, 1, true>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,          \
+        t_launch_bwd<NT_, DT_, 1, 1>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,          \
                                         (const uint8_t*)ref_idx, ref_val, seed_coef, s, 1, row_w);                         \
     else                                                                                                                   \
-        t_launch_bwd<NT_, DT_, MC_TATTN_KMAX, true>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg, \
+        t_launch_bwd<NT_, DT_, MC_TATTN_KMAX, 1>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg, \
                                                     (const uint8_t*)ref_idx, ref_val, seed_coef, s, K, row_w)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// Motion composition: the slots of a query row are the entries of R references concatenated, K = sum K_r in 1 .. 8 (not bound by
+// F), slot_w f32 [B*HW, F, K] = lambda_r * w_r[bn, f] / K_r per slot (heads share it).
+// loss[0] = 1 / (B*HW*heads*F) * sum slot_w[bn, f, s] * (P[q, idx[q][s]] - ref[q][s])^2: no K in the denominator, it lives in the
+// weights.  A null ref_idx / ref_val / slot_w or another K returns the shape error with nothing launched.
+extern "C" int mc_tattn_loss_slotw_f16(const void* q, const void* k, int ld, const void* ref_idx, const float* ref_val,
+                                       int K, const float* slot_w, float* unit_loss, float* loss, int B, int F, int HW,
+                                       int heads, int d, float scale, void* stream) {
+    TParams P = t_params(q, k, k, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_slots(K) || !ref_idx || !ref_val || !slot_w) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                    \
+    t_launch_fwd<NT_, DT_, MC_TATTN_KMAX, 2>(P, nullptr, 0, 2, nullptr, nullptr, (const uint8_t*)ref_idx, ref_val, unit_loss, s, \
+                                             K, slot_w)
+    MC_T_DISPATCH(CALL)
+#undef CALL
+    long units = (long)B * HW * heads;
+    MC_LAUNCH(reduce_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)unit_loss, units,
+              1.0f / (float)(units * F), loss);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// dP[q, idx[q][s]] += seed_coef * slot_w[bn, q, s] * (P[q, idx[q][s]] - ref[q][s]) for every s < K, in the order of s: a frame
+// named in two slots gets both seeds.  dO may be NULL; ref_idx / ref_val / slot_w are required.
+extern "C" int mc_tattn_bwd_slotw_f16(const void* q, const void* k, const void* v, int ld, const void* dO, int lddo,
+                                      void* dq, void* dk, void* dv, int ldg, const void* ref_idx, const float* ref_val,
+                                      int K, const float* slot_w, float seed_coef, int B, int F, int HW, int heads, int d,
+                                      float scale, void* stream) {
+    TParams P = t_params(q, k, v, ld, B, F, HW, heads, d, scale);
+    if (!t_check(P) || !t_check_slots(K) || ldg % 4 || (dO && lddo % 4)) return MC_ERR_SHAPE;
+    if (!ref_idx || !ref_val || !slot_w) return MC_ERR_SHAPE;
+    int nt = (F + 15) / 16, dt = (d + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(NT_, DT_)                                                                                                  \
+    t_launch_bwd<NT_, DT_, MC_TATTN_KMAX, 2>(P, (const half_t*)dO, lddo, (half_t*)dq, (half_t*)dk, (half_t*)dv, ldg,  \
+                                             (const uint8_t*)ref_idx, ref_val, seed_coef, s, K, slot_w)
     MC_T_DISPATCH(CALL)
 #undef CALL
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;

@@ -552,7 +552,8 @@ class UNet3DEngine:
     def _motion(self, name, x, geo, tape, record, seeds):
         """VanillaTemporalModule (motion_module.py:80-85,137-161,213-225,274-345).
         record: dict collecting the fused q|k|v buffer of hooked attentions (MySelfAttnProcessor.record_qkv);
-        seeds: {attention name: (ref_idx u8, ref_val f32, coef[, row weights f32 [BN, F] or None])} guidance seeds for the backward."""
+        seeds: {attention name: (ref_idx u8, ref_val f32, coef[, row weights f32 [BN, F] / slot weights f32 [BN, F, K] or None])}
+        guidance seeds for the backward."""
         w, cfg = self.w, self.cfg
         heads = cfg["motion_heads"]
         C = x.shape[1]
@@ -612,7 +613,7 @@ class UNet3DEngine:
                 ops.tattn_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], da, dqkv[:, :C], dqkv[:, C:2 * C],
                               dqkv[:, 2 * C:], g1.B, g1.F, hw1, heads, d,
                               ref_idx=seed[0] if seed else None, ref_val=seed[1] if seed else None,
-                              seed_coef=seed[2] if seed else 0.0, row_w=seed[3] if seed and len(seed) > 3 else None)
+                              seed_coef=seed[2] if seed else 0.0, **self._weight_kw(seed[3] if seed and len(seed) > 3 else None))
                 dn = ops.gemm(dqkv, w.cat_lin_t([ap + "to_q.weight", ap + "to_k.weight", ap + "to_v.weight"]))
                 dh = ops.layernorm_bwd(dn, hin, ls, w.vec(b + "norms.%d.weight" % a), add=dh)
             dhn = ops.gemm(dh, w.lin_t(p + "proj_in.weight"))
@@ -824,7 +825,7 @@ class UNet3DEngine:
                     for v in range(V)]
         return rep
 
-    def prepare_representation(self, rep, frames=None, mask=None, mask_normalize=False, grid=None):
+    def prepare_representation(self, rep, frames=None, mask=None, mask_normalize=False, grid=None, references=None):
         """reference .pt dict {name: [values [BN, heads, F, K], indices uint8]} -> device tensors for the kernels; K is the
         sparsity of the representation (1 in the reference's own files, 1 <= K <= min(F, 8) here), one K for all entries.
         A LIST of such dicts (V videos batched in one forward, guided_eps_and_grad) is concatenated along the (b, pixel) axis
@@ -837,7 +838,17 @@ class UNet3DEngine:
         then carries a third element, the fp32 row weights [BN, F] of that module - the mask's area mean over the block each
         position covers, reduced HERE, once per video (the steps only read them); videos of a packed batch without a mask
         get ones.  `mask_normalize`: the weights of each video and module are divided by their mean (ValueError where that
-        is 0).  With no mask anywhere the entries stay two-tuples and nothing downstream changes."""
+        is 0).  With no mask anywhere the entries stay two-tuples and nothing downstream changes.
+        `references` (motion composition): further motion references of the video, a list of dicts {representation, weight =
+        1.0, mask = None, mask_normalize = False}; for a list of representations a list of such lists with None entries.
+        Reference 0 is `rep` with `mask` (weight 1).  Every further reference has the modules, BN, heads and F of `rep`, its
+        own top-k K_r, a weight lambda_r >= 0 (0: the reference is dropped) and optionally a mask of its own; the K_r sum to
+        at most 8.  A module's entry is then (idx, val, slot_w): the references' entries concatenated along the last axis in
+        reference order, and the fp32 slot weights [BN, F, K], slot_w[bn, f, s] = lambda_r * w_r[bn, f] / K_r for a slot of
+        reference r - built here on the host in float64, once per video.  In a packed batch where any video has references
+        every video takes this form (one without references: w_0 / K_0), rows of fewer slots padded to the batch's largest K
+        with slots of weight 0, index 0, value 0.  With no references anywhere entries and launches are as without the
+        argument."""
         if isinstance(rep, (list, tuple)):
             V = len(rep)
             if isinstance(mask, (list, tuple)):
@@ -846,9 +857,19 @@ class UNet3DEngine:
                 masks = list(mask)
             else:
                 masks = [mask] * V
-            parts = [self.prepare_representation(r, frames, m, mask_normalize, grid) for r, m in zip(rep, masks)]
-            if len(parts) == 1:
-                return parts[0]
+            if references is None:
+                refs = [None] * V
+            else:
+                if len(references) != V or any(isinstance(r, dict) for r in references):
+                    raise ValueError("motion references: %d motion representations need a list of %d reference lists (None "
+                                     "where a video has none), got %d entries" % (V, V, len(references)))
+                refs = list(references)
+            vids = [self._prepare_video(r, frames, m, mask_normalize, grid, rf) for r, m, rf in zip(rep, masks, refs)]
+            if len(vids) == 1:
+                return self._finish_entries(vids[0])
+            if any(e[3] is not None for v in vids for e in v.values()):
+                return self._pack_composed(vids)
+            parts = [self._finish_entries(v) for v in vids]
             ks = [representation_k(p) for p in parts]
             if len(set(ks)) != 1:
                 raise ValueError("the motion representations of one packed batch differ in their top-k: %s" % ks)
@@ -861,6 +882,23 @@ class UNet3DEngine:
                                           for p in parts], 0).contiguous())
                 out[name] = tuple(ent)
             return out
+        return self._finish_entries(self._prepare_video(rep, frames, mask, mask_normalize, grid, references))
+
+    def _finish_entries(self, vid):
+        """{name: (idx, val, row weights float64 or None, slot weights float64 or None)} -> the entries the steps read"""
+        out = {}
+        for name, (idx, val, w64, slot64) in vid.items():
+            if slot64 is not None:
+                out[name] = (idx, val, slot64.to(self.dev, torch.float32).contiguous())
+            elif w64 is not None:
+                out[name] = (idx, val, w64.to(self.dev, torch.float32).contiguous())
+            else:
+                out[name] = (idx, val)
+        return out
+
+    def _prepare_one(self, rep, frames, mask, mask_normalize, grid):
+        """one reference of one video, validated: {name: (idx u8, val f32 on the device, row weights [BN, F] float64 on the
+        host or None without a mask)}"""
         mask64 = None
         if mask is not None:
             if grid is None:
@@ -880,7 +918,7 @@ class UNet3DEngine:
                                  % (name, vs, vs[3], vs[2], MAX_TOPK))
             if frames is not None and vs[2] != int(frames):
                 raise ValueError("motion representation %s: shape %s holds %d frames, the run has %d" % (name, vs, vs[2], int(frames)))
-            out[name] = (idx.to(self.dev, torch.uint8).contiguous(), val.to(self.dev, torch.float32).contiguous())
+            w = None
             if mask64 is not None:
                 w = reduce_motion_mask(mask64, grid, vs[0])
                 if mask_normalize:
@@ -888,12 +926,81 @@ class UNet3DEngine:
                     if mean == 0.0:
                         raise ValueError("motion mask: motion_mask_normalize with a mask whose mean over %s is 0" % name)
                     w = w / mean
-                out[name] = out[name] + (w.to(self.dev, torch.float32).contiguous(),)
+            out[name] = (idx.to(self.dev, torch.uint8).contiguous(), val.to(self.dev, torch.float32).contiguous(), w)
         ks = sorted({e[0].shape[3] for e in out.values()})
         if len(ks) > 1:
             raise ValueError("the entries of one motion representation differ in their top-k: %s"
                              % {n: tuple(e[0].shape) for n, e in out.items()})
         return out
+
+    @staticmethod
+    def _slots64(idx, w64, lam=1.0):
+        """slot weights [BN, F, K] (float64, host) of one reference: lam * w[bn, f] / K in each of its K slots"""
+        BN, _, F, K = idx.shape
+        w = w64 if w64 is not None else torch.ones((BN, F), dtype=torch.float64)
+        return (float(lam) * w / float(K)).unsqueeze(-1).expand(-1, -1, K)
+
+    def _prepare_video(self, rep, frames, mask, mask_normalize, grid, references):
+        """one video: {name: (idx, val, row weights float64 or None, slot weights float64 [BN, F, K] or None)}; the last
+        element is set when the video has references of a weight above 0 (the entries are then the merged ones)"""
+        prim = self._prepare_one(rep, frames, mask, mask_normalize, grid)
+        if references is not None and isinstance(references, dict):
+            raise ValueError("motion references: a list of reference dicts is expected, got one dict")
+        extra = []
+        for r, ref in enumerate(references or (), 1):
+            if not isinstance(ref, dict) or ref.get("representation") is None:
+                raise ValueError("motion reference %d: a dict {representation, weight, mask, mask_normalize} is expected" % r)
+            lam = float(ref.get("weight", 1.0))
+            if not math.isfinite(lam) or lam < 0.0:
+                raise ValueError("motion reference %d: weight %r is negative or not finite" % (r, ref.get("weight")))
+            if lam == 0.0:
+                continue        # dropped before the slots are counted: the run is the one without it
+            one = self._prepare_one(ref["representation"], frames, ref.get("mask"), bool(ref.get("mask_normalize", False)), grid)
+            if set(one) != set(prim):
+                raise ValueError("motion reference %d: its modules differ from those of the example's own reference (missing %s, "
+                                 "foreign %s)" % (r, sorted(set(prim) - set(one)), sorted(set(one) - set(prim))))
+            for name, e in prim.items():
+                if tuple(one[name][0].shape[:3]) != tuple(e[0].shape[:3]):
+                    raise ValueError("motion reference %d, %s: shape %s against [BN = %d, heads = %d, F = %d, K] of the example's own "
+                                     "reference" % ((r, name, tuple(one[name][0].shape)) + tuple(e[0].shape[:3])))
+            extra.append((lam, one))
+        if not extra:
+            return {name: e + (None,) for name, e in prim.items()}
+        ks = [representation_k(prim)] + [representation_k(one) for _, one in extra]
+        if sum(ks) > MAX_TOPK:
+            raise ValueError("motion references: the top-k of the %d references of one video %s sum to %d slots per row, at most %d "
+                             "fit" % (len(ks), ks, sum(ks), MAX_TOPK))
+        out = {}
+        for name, e in prim.items():
+            parts = [(1.0, e)] + [(lam, one[name]) for lam, one in extra]
+            out[name] = (torch.cat([p[0] for _, p in parts], -1).contiguous(), torch.cat([p[1] for _, p in parts], -1).contiguous(),
+                         None, torch.cat([self._slots64(p[0], p[2], lam) for lam, p in parts], -1).contiguous())
+        return out
+
+    def _pack_composed(self, vids):
+        """a packed batch in which some video has references: every video in the slot-weighted form (one without references:
+        w_0 / K_0 per slot), rows padded to the batch's largest K with slots of weight 0, index 0, value 0"""
+        out = {}
+        for name in vids[0]:
+            ents = []
+            for v in vids:
+                idx, val, w64, slot64 = v[name]
+                ents.append((idx, val, slot64 if slot64 is not None else self._slots64(idx, w64)))
+            K = max(e[0].shape[3] for e in ents)
+
+            def pad(t, K=K):
+                return t if t.shape[-1] == K else torch.nn.functional.pad(t, (0, K - t.shape[-1]))
+            out[name] = (torch.cat([pad(e[0]) for e in ents], 0).contiguous(), torch.cat([pad(e[1]) for e in ents], 0).contiguous(),
+                         torch.cat([pad(e[2]) for e in ents], 0).to(self.dev, torch.float32).contiguous())
+        return out
+
+    @staticmethod
+    def _weight_kw(w):
+        """the weight argument of ops.tattn_loss / tattn_bwd for the third element of an entry: row weights [BN, F] (a motion
+        mask) or slot weights [BN, F, K] (several references) - the launches differ"""
+        if w is None:
+            return {}
+        return dict(slot_w=w) if w.dim() == 3 else dict(row_w=w)
 
     @ops.scoped
     def guided_eps_and_grad(self, latents, t, text_cond, rep_dev, weight, want_loss=False, down_residuals=None,
@@ -936,6 +1043,10 @@ class UNet3DEngine:
         for name, ent in rep_dev.items():
             idx, val = ent[0], ent[1]
             numel = idx.numel() // V              # per video: F.mse_loss averages over ONE video's map (all K entries per row)
+            if len(ent) == 3 and ent[2].dim() == 3:
+                # several references (slot weights [BN, F, K]): every reference's own 1 / K_r lives in its slots' weights,
+                # the denominator left for the coefficient is the rows of one video, BN heads F
+                numel //= idx.shape[-1]
             seeds[name] = (idx, val, tape.grad_scale * float(weight) * 2.0 / numel, ent[2] if len(ent) == 3 else None)
         record = {}
         if batched:
@@ -959,7 +1070,7 @@ class UNet3DEngine:
                 r = record[name]
                 C, g = r["C"], r["geo"]
                 lm = ops.tattn_loss(r["qkv"][:, :C], r["qkv"][:, C:2 * C], ent[0], ent[1], g.B, g.F, g.hw, r["heads"], r["d"],
-                                    row_w=ent[2] if len(ent) == 3 else None)
+                                    **self._weight_kw(ent[2] if len(ent) == 3 else None))
                 total = lm if total is None else total + lm
             loss = total * (float(weight) * V)   # tattn_loss is the mean over all V maps; the sum of the V means is V x that
         tape.latent_grad = None

@@ -92,6 +92,18 @@ class Group:
         return results[[s for s, _ in items].index(slot)]
 
 
+def set_example(line):
+    """the launcher's note for the calling thread: the parsed examples-file line its script is working on (None: none).  The
+    entry scripts read a fixed set of keys from a line; optional per-example keys of this package (`motion_references`) are
+    looked up here by the drop-in functions."""
+    _LOCAL.example = line
+
+
+def example():
+    """the examples-file line of the calling thread's current example ({} outside a launcher run)"""
+    return getattr(_LOCAL, "example", None) or {}
+
+
 def begin(lane, n_lanes, device, slot=0, group=None):
     """mark the calling thread as slot `slot` of lane `lane` of `n_lanes`; its serial-RNG stream lives on `device`; `group` is the
     lane's `Group` when the lane carries several examples per launch sequence"""

@@ -127,10 +127,12 @@ class _ShardedLines(io.StringIO):
                     if n == 1 and self._first_end:       # asked for the second line = the first example is finished
                         self._first_end()
                     n += 1
+                    mcl.set_example(json.loads(ln))      # per-example keys the scripts do not read (motion_references)
                     yield ln
                 elif self._burn is not None:
                     self._burn(json.loads(ln))
         finally:
+            mcl.set_example(None)
             if self._on_end:                             # first: the fellow members must not wait for this thread any more
                 self._on_end()
             if n == 0 and self._first_begin:             # a lane without examples still takes its turn
@@ -210,8 +212,12 @@ def main(argv=None):
     real_open = builtins.open
     ex_abs = os.path.abspath(examples)
 
+    # lines that carry per-example keys of this package are handed out by _ShardedLines also where nothing is sharded: it
+    # notes the current line for the drop-in functions (lanes.example)
+    line_keys = any('"motion_references"' in ln for ln in lines)
+
     def sharded_open(path, *a, **k):
-        if sharded and isinstance(path, (str, os.PathLike)) and os.path.abspath(path) == ex_abs and (not a or "r" in a[0]):
+        if (sharded or line_keys) and isinstance(path, (str, os.PathLike)) and os.path.abspath(path) == ex_abs and (not a or "r" in a[0]):
             me = (rank, mcl.lane_index() or 0, mcl.slot_index() or 0)
             fb, fe = (warm_begin, warm_end) if n_threads > 1 else (None, None)
             if n_threads > 1:    # the thread has built its models (their H2D copies synchronise): it is ready for the warm-up turns
@@ -219,7 +225,7 @@ def main(argv=None):
                     warm_state["ready"] += 1
                     warm_turn.notify_all()
             grp, slot = mcl.group(), mcl.slot_index()
-            return _ShardedLines(lines, rank, world, burn if serial_rng else None, fb, fe,
+            return _ShardedLines(lines, rank, world, burn if serial_rng and sharded else None, fb, fe,
                                  owns=lambda i: assign(i, world, n_lanes, batch)[:3] == me,
                                  on_end=(lambda: grp.leave(slot)) if grp is not None else None)
         return real_open(path, *a, **k)

@@ -60,6 +60,8 @@ SIGNATURES = {
     "mc_tattn_bwd_topk_f16": [P, P, P, I, P, I, P, P, P, I, P, P, I, F, I, I, I, I, I, F, P],
     "mc_tattn_loss_weighted_f16": [P, P, I, P, P, I, P, P, P, I, I, I, I, I, F, P],
     "mc_tattn_bwd_weighted_f16": [P, P, P, I, P, I, P, P, P, I, P, P, I, P, F, I, I, I, I, I, F, P],
+    "mc_tattn_loss_slotw_f16": [P, P, I, P, P, I, P, P, P, I, I, I, I, I, F, P],
+    "mc_tattn_bwd_slotw_f16": [P, P, P, I, P, I, P, P, P, I, P, P, I, P, F, I, I, I, I, I, F, P],
     "mc_tattn_prob_f16": [P, P, I, P, I, I, I, I, I, F, P],
     "mc_tattn_loss_f16": [P, P, I, P, P, P, P, I, I, I, I, I, F, P],
     "mc_tattn_bwd_f16": [P, P, P, I, P, I, P, P, P, I, P, P, F, I, I, I, I, I, F, P],

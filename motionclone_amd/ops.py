@@ -551,15 +551,34 @@ def _row_w(row_w, BN, F):
     return row_w
 
 
-def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None, row_w=None):
+def _slot_w(slot_w, BN, F, K):
+    """slot weights of a composed guidance (several references): fp32, contiguous, [BN, F, K] - one per (b, pixel), query frame
+    and slot, lambda_r * w_r[bn, f] / K_r for a slot of reference r"""
+    if slot_w.dtype != torch.float32:
+        raise ValueError("slot_w must be float32, got %s" % slot_w.dtype)
+    if not slot_w.is_contiguous():
+        raise ValueError("slot_w must be contiguous")
+    if tuple(slot_w.shape) != (BN, F, K):
+        raise ValueError("slot_w %s for [BN = %d, F = %d, K = %d]" % (tuple(slot_w.shape), BN, F, K))
+    return slot_w
+
+
+def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None, row_w=None, slot_w=None):
     """mean((gather(P, ref_idx) - ref_val)^2) over all entries; the sparsity K is ref_idx.shape[-1].
     `row_w` [BN, F]: every squared error of query frame f at (b, pixel) is weighted by row_w[bn, f]; the mean keeps the
-    unweighted denominator.  None: the unweighted entries."""
+    unweighted denominator.  None: the unweighted entries.
+    `slot_w` [BN, F, K] (not together with row_w): the K slots of a row are the entries of several references and each squared
+    error is weighted by its slot's entry; the denominator is BN * heads * F (the K_r live in the weights), 1 <= K <= 8."""
     scale = d ** -0.5 if scale is None else scale
+    if row_w is not None and slot_w is not None:
+        raise ValueError("row_w and slot_w are mutually exclusive: slot weights carry the row weights of every reference")
     K = _seed_k(ref_idx, ref_val, B * HW, heads, F)
     ul = workspace("tattn_loss", q, B, HW, heads)
     loss = empty((1,), q, torch.float32)
-    if row_w is not None:
+    if slot_w is not None:
+        lib.call("mc_tattn_loss_slotw_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), K, _p(_slot_w(slot_w, B * HW, F, K)),
+                 _p(ul), _p(loss), B, F, HW, heads, d, float(scale), _stream(q))
+    elif row_w is not None:
         lib.call("mc_tattn_loss_weighted_f16", _p(q), _p(k), _ld(q), _p(ref_idx), _p(ref_val), K, _p(_row_w(row_w, B * HW, F)),
                  _p(ul), _p(loss), B, F, HW, heads, d, float(scale), _stream(q))
     elif K == 1:
@@ -572,11 +591,21 @@ def tattn_loss(q, k, ref_idx, ref_val, B, F, HW, heads, d, scale=None, row_w=Non
 
 
 def tattn_bwd(q, k, v, do, dq, dk, dv, B, F, HW, heads, d, ref_idx=None, ref_val=None, seed_coef=0.0,
-              scale=None, row_w=None):
-    """`row_w` [BN, F] (needs the seed): the seed of query frame f at (b, pixel) is scaled by row_w[bn, f]"""
+              scale=None, row_w=None, slot_w=None):
+    """`row_w` [BN, F] (needs the seed): the seed of query frame f at (b, pixel) is scaled by row_w[bn, f]
+    `slot_w` [BN, F, K] (needs the seed, not together with row_w): the seed of slot s of that row is scaled by slot_w[bn, f, s]"""
     scale = d ** -0.5 if scale is None else scale
     assert _ld(q) == _ld(k) == _ld(v) and _ld(dq) == _ld(dk) == _ld(dv)
+    if row_w is not None and slot_w is not None:
+        raise ValueError("row_w and slot_w are mutually exclusive: slot weights carry the row weights of every reference")
     K = 1 if ref_idx is None else _seed_k(ref_idx, ref_val, B * HW, heads, F)
+    if slot_w is not None:
+        if ref_idx is None:
+            raise ValueError("slot_w weights the guidance seed: ref_idx / ref_val are required")
+        lib.call("mc_tattn_bwd_slotw_f16", _p(q), _p(k), _p(v), _ld(q), _p(do), _ld(do), _p(dq), _p(dk), _p(dv), _ld(dq),
+                 _p(ref_idx), _p(ref_val), K, _p(_slot_w(slot_w, B * HW, F, K)), float(seed_coef), B, F, HW, heads, d,
+                 float(scale), _stream(q))
+        return
     if row_w is not None:
         if ref_idx is None:
             raise ValueError("row_w weights the guidance seed: ref_idx / ref_val are required")

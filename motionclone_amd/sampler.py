@@ -135,8 +135,10 @@ class MotionCloneSampler:
         condition - enters through static buffers that are refreshed by copies before
         the replay, so a graph captured on the first video serves every later (prompt, reference-video) pair."""
         guided = i < self.G
-        # (name, shape, weighted?): a motion mask adds the row weights as a third static buffer and runs other kernels
-        rsig = tuple((k, tuple(v[0].shape), len(v) == 3) for k, v in rep_dev.items()) if guided else ()
+        # (name, shape, weighted?, slot-weighted?): a motion mask adds the row weights as a third static buffer and runs other
+        # kernels; several references add slot weights [BN, F, K] instead (K, the slots per row, is part of the shape) and run
+        # yet other kernels.  Other references of the same shapes are a copy into the static buffers, not a capture.
+        rsig = tuple((k, tuple(v[0].shape), len(v) == 3, len(v) == 3 and v[2].dim() == 3) for k, v in rep_dev.items()) if guided else ()
         csig = None if ctrl is None else (tuple(ctrl["cond"].shape), tuple(ctrl["mask"].shape), float(ctrl.get("scale", 1.0)))
         key = (i, tuple(latents.shape), tuple(text.shape), rsig, csig, self._gemm_share())   # the GEMM geometry is baked in
         ent = self._graphs.get(key)
@@ -218,7 +220,8 @@ class MotionCloneSampler:
     def _step_eager(self, latents, i, text, rep_dev, aux=None, ctrl=None, sigma=0.0):
         """latents [V, 4, F, H, W]; text [2 V, n, dim] ordered [u_1 .. u_V | c_1 .. c_V] (V = 1: [uncond, cond], the reference's
         layout); rep_dev: engine.prepare_representation of the V representations (a list for V > 1), its entries two-tuples or,
-        with a motion mask, three-tuples whose last element is the row weights [BN, F].  V > 1 = V independent
+        with a motion mask, three-tuples whose last element is the row weights [BN, F], with several references per video
+        three-tuples whose last element is the slot weights [BN, F, K].  V > 1 = V independent
         videos through ONE launch sequence (same kernels, V times the rows): each video's arithmetic is its own - no
         reduction crosses the batch - but the GEMM tile / split-K choice follows the larger row count, so results agree
         with the one-video path to fp16 rounding, not bit for bit.  ctrl: `cond` [V, ...] / `mask` [V, 1, ...] carry one
@@ -267,10 +270,11 @@ class MotionCloneSampler:
             aux.update(eps_u=eps2[:T1], eps_c=eps2[T1:])
         return update(eps2[T1:], eps2[:T1], None, 0.0)
 
-    def sample(self, latents, text, rep, progress=None, ctrl=None, mask=None, mask_normalize=False):
-        """`mask`: a motion mask (a list with None entries for V > 1), see engine.prepare_representation"""
+    def sample(self, latents, text, rep, progress=None, ctrl=None, mask=None, mask_normalize=False, references=None):
+        """`mask`: a motion mask (a list with None entries for V > 1), `references`: further motion references of the video
+        (a list of such lists with None entries for V > 1), see engine.prepare_representation"""
         rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2], mask=mask, mask_normalize=mask_normalize,
-                                                     grid=tuple(latents.shape[3:]))
+                                                     grid=tuple(latents.shape[3:]), references=references)
         for i in range(len(self.timesteps)):
             latents = self.step(latents, i, text, rep_dev, ctrl=ctrl)
             if progress is not None:
@@ -294,7 +298,7 @@ def batch_ctrl(entry, V):
     return dict(cond=torch.cat([c["cond"] for c in entry], 0), mask=torch.cat([c["mask"] for c in entry], 0), scale=scales.pop())
 
 
-def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=None, on_step=None):
+def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=None, on_step=None, references=None):
     """Several independent videos in flight on one GPU (examples are the unit of parallelism).
 
     `jobs[k] = (latents, text [2,77,768], reference_video_latents, extraction_noise)` - or a LIST of such tuples: V videos
@@ -307,7 +311,9 @@ def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=No
     step inside the lane's stream context (bench.py records its events there).  `streams=None` issues everything on the
     current stream (same issue order, no overlap; what the host-simulator tests use).  `ctrl`: one SparseCtrl dict for every
     job, or a LIST with one entry per job - a dict, or for a batched job a list of per-video dicts / an already batched dict
-    (`batch_ctrl`).  Returns the final latents per job."""
+    (`batch_ctrl`).  `references`: further motion references, one entry per job - None, the reference list of a one-video job,
+    or for a batched job a list of such lists with None entries (engine.prepare_representation).  Returns the final latents
+    per job."""
     n = len(jobs)
     if n == 0:
         return []
@@ -323,6 +329,8 @@ def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=No
             st.wait_stream(cur)
     if isinstance(ctrl, (list, tuple)) and len(ctrl) != n:
         raise ValueError("sample_interleaved: %d ctrl entries for %d jobs" % (len(ctrl), n))
+    if references is not None and len(references) != n:
+        raise ValueError("sample_interleaved: %d references entries for %d jobs" % (len(references), n))
     xs, reps, texts, ctrls = [None] * n, [None] * n, [None] * n, [None] * n
     for k, job in enumerate(jobs):
         vids = job if isinstance(job, list) else [job]       # a LIST of videos on one lane = one batched launch sequence
@@ -337,7 +345,11 @@ def sample_interleaved(samplers, jobs, streams=None, add_noise_step=400, ctrl=No
                                          torch.cat([v[1][0:1] for v in vids], 0), add_noise_step=add_noise_step, ctrl=ctrls[k])
                 xs[k] = torch.cat([v[0] for v in vids], 0)
                 texts[k] = torch.cat([v[1][0:1] for v in vids] + [v[1][1:2] for v in vids], 0)
-            reps[k] = samplers[k].engine.prepare_representation(rr)
+            if references is None or references[k] is None:
+                reps[k] = samplers[k].engine.prepare_representation(rr)
+            else:
+                reps[k] = samplers[k].engine.prepare_representation(rr, frames=xs[k].shape[2], grid=tuple(xs[k].shape[3:]),
+                                                                    references=references[k])
     for i in range(len(samplers[0].timesteps)):
         for k in range(n):
             with lane(k):

@@ -117,6 +117,50 @@ def _motion_mask(pipe, override=None):
     return _load_mask(m), bool(getattr(cfg, "motion_mask_normalize", False) or False)
 
 
+_REFERENCE_KEYS = ("representation_path", "representation", "weight", "mask_path", "mask", "mask_normalize")
+
+
+def _motion_references(pipe, override=None):
+    """further motion references of the next sampling run (motion composition; engine.prepare_representation `references`): a
+    per-call / per-example override, else the `motion_references` key of the examples-file line a launcher thread is working
+    on, else the pipeline attribute `motion_references`, else the optional inference-yaml key `motion_references` - a list of
+    {representation_path: x.pt (a file written by obtain_motion_representation, any motion_topk) or representation: the
+    loaded dict, weight: 1.0, mask_path: m.pt | m.npy (or mask: a tensor), mask_normalize: false}.  None / empty = no further
+    reference, every path as without the feature.  The example's own reference keeps `motion_mask_path`."""
+    from .. import lanes
+    from ..checkpoints import _real_torch_load
+    refs = override
+    if refs is None:
+        refs = lanes.example().get("motion_references")
+    if refs is None:
+        refs = getattr(pipe, "motion_references", None)
+    if refs is None:
+        refs = getattr(pipe.input_config, "motion_references", None)
+    if refs is None or len(refs) == 0:
+        return None
+    out = []
+    for r, ref in enumerate(refs, 1):
+        if isinstance(ref, (str, bytes)) or not hasattr(ref, "keys"):
+            raise ValueError("motion_references entry %d: a mapping {representation_path, weight, mask_path, mask_normalize} is "
+                             "expected, got %r" % (r, ref))
+        ref = {k: ref[k] for k in ref.keys()}
+        unknown = sorted(set(ref) - set(_REFERENCE_KEYS))
+        if unknown:
+            raise ValueError("motion_references entry %d: unknown keys %s (known: %s)" % (r, unknown, list(_REFERENCE_KEYS)))
+        rep = ref.get("representation")
+        if rep is None:
+            path = ref.get("representation_path")
+            if path is None:
+                raise ValueError("motion_references entry %d: representation_path (or representation) is missing" % r)
+            rep = _real_torch_load(os.fspath(path), map_location="cpu")     # the per-example file, read by the thread that uses it
+        mask = ref.get("mask")
+        w = ref.get("weight")
+        out.append(dict(representation=rep, weight=1.0 if w is None else float(w),
+                        mask=_load_mask(mask if mask is not None else ref.get("mask_path")),
+                        mask_normalize=bool(ref.get("mask_normalize") or False)))
+    return out
+
+
 @torch.no_grad()
 def obtain_motion_representation(self, generator=None, motion_representation_path: str = None, duration=None,
                                  use_controlnet=False, video_latents=None, uncond_embeddings=None, video_data=None,
@@ -233,9 +277,16 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
     if not hasattr(self, "_mc_mask"):            # called without sample_video: the configured mask, read once
         self._mc_mask = _motion_mask(self)
     mask, mask_norm = self._mc_mask
+    if not hasattr(self, "_mc_refs"):            # called without sample_video: the configured further references, read once
+        self._mc_refs = _motion_references(self)
     if (getattr(self, "_mc_rep_src", None) is not self.motion_representation_dict
-            or getattr(self, "_mc_rep_mask", None) is not self._mc_mask):
-        if mask is None:
+            or getattr(self, "_mc_rep_mask", None) is not self._mc_mask
+            or getattr(self, "_mc_rep_refs", None) is not self._mc_refs):
+        if self._mc_refs is not None:            # motion composition: merged with the example's own reference here, once per video
+            self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2],
+                                                                 mask=mask, mask_normalize=mask_norm,
+                                                                 grid=tuple(noisy_latents.shape[3:]), references=self._mc_refs)
+        elif mask is None:
             self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2])
         else:                                    # reduced to the hooked modules' grids here, once per video
             self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2],
@@ -243,6 +294,7 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
                                                                  grid=tuple(noisy_latents.shape[3:]))
         self._mc_rep_src = self.motion_representation_dict
         self._mc_rep_mask = self._mc_mask
+        self._mc_rep_refs = self._mc_refs
     kw = dict(extra_step_kwargs or {})      # prepare_extra_step_kwargs: eta / generator, handed to customized_step (:241,255)
     out = smp.step(noisy_latents.half(), step_index, self.text_embeddings.half(), self._mc_rep_dev, ctrl=ctrl,
                    eta=float(kw.get("eta", 0.0) or 0.0), generator=kw.get("generator") if kw.get("eta") else None)
@@ -254,12 +306,16 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
 
 
 def sample_video(self, eta: float = 0.0, generator=None, noisy_latents: Optional[torch.Tensor] = None,
-                 add_controlnet: bool = False, text_embeddings=None, decode=True, controlnet_images=None, motion_mask=None):
+                 add_controlnet: bool = False, text_embeddings=None, decode=True, controlnet_images=None, motion_mask=None,
+                 motion_references=None):
     """:102-171.  `motion_mask` (tensor or path; default: the pipeline attribute `motion_mask`, then the yaml key
-    `motion_mask_path`): region weights of the guidance for this video."""
+    `motion_mask_path`): region weights of the guidance for this video.  `motion_references` (default: the examples-file
+    line's, the pipeline attribute's, then the yaml key's `motion_references`): further motion references that guide this
+    video beside its own (`_motion_references`)."""
     self.add_controlnet = add_controlnet
     cfg = self.input_config
     self._mc_mask = _motion_mask(self, motion_mask)
+    self._mc_refs = _motion_references(self, motion_references)
     if add_controlnet and controlnet_images is not None:
         # already what the ControlNet consumes (:122-128): VAE latents [1, 4, n, h, w], or pixels in [0, 1] [1, 3, n, H, W]
         self.controlnet_images = controlnet_images
@@ -336,11 +392,12 @@ _MIXED = "either every example carries a condition image or none does"
 
 
 @torch.no_grad()
-def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None, masks=None):
+def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None, masks=None, references=None):
     """The packed step loop on this pipeline's sampler for V videos whose per-example host work is done: `latents` V tensors
     [1, 4, F, H, W], `texts` V [2, n, dim] ([uncond, cond]), `reps` V motion representations, `ctrls` V SparseCtrl dicts
     (cond / mask [1, ...] placed at image_index, scale) or V times None, `generators` the V generators that `eta > 0` draws each
-    video's variance noise from, in list order at every step, `masks` V motion masks (tensors or None; None = no mask at all).
+    video's variance noise from, in list order at every step, `masks` V motion masks (tensors or None; None = no mask at all),
+    `references` V lists of further motion references (`_motion_references`) or None (None = none at all).
     Returns the final latents [V, 4, F, H, W] - after a replayed
     step the graph's static buffer: callers that keep them copy."""
     from ..sampler import batch_ctrl
@@ -354,7 +411,12 @@ def _packed_sample(self, latents, texts, reps, ctrls, eta=0.0, generators=None, 
     if use_ctrl[0]:
         smp.controlnet = self.controlnet.engine()
         ctrl = batch_ctrl(list(ctrls), V)
-    if masks is None or all(m is None for m in masks):
+    if references is not None and any(r is not None for r in references):
+        rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2],
+                                                    mask=list(masks) if masks is not None else None,
+                                                    mask_normalize=_motion_mask(self)[1], grid=tuple(latents[0].shape[3:]),
+                                                    references=list(references))
+    elif masks is None or all(m is None for m in masks):
         rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2])   # one top-k K for the V videos
     else:
         rep_dev = smp.engine.prepare_representation(list(reps), frames=latents[0].shape[2], mask=list(masks),
@@ -391,7 +453,7 @@ def _run_group(grp, items):
     def run():
         x = _packed_sample(pipe, [it["latents"] for it in items], [it["text"] for it in items], [it["rep"] for it in items],
                            [it["ctrl"] for it in items], eta=etas.pop(), generators=[it["generator"] for it in items],
-                           masks=[it.get("mask") for it in items])
+                           masks=[it.get("mask") for it in items], references=[it.get("references") for it in items])
         return [x[v:v + 1].clone() for v in range(len(items))]
     if not on_gpu:
         return [(o, None) for o in run()]
@@ -422,7 +484,8 @@ def _group_sample(self, grp, noisy_latents, eta, generator):
         ready = torch.cuda.Event()
         ready.record()
     item = dict(pipe=self, latents=noisy_latents, text=self.text_embeddings, rep=self.motion_representation_dict, ctrl=ctrl,
-                eta=float(eta or 0.0), generator=generator, ready=ready, mask=self._mc_mask[0])
+                eta=float(eta or 0.0), generator=generator, ready=ready, mask=self._mc_mask[0],
+                references=getattr(self, "_mc_refs", None))
     out = grp.meet(lanes.slot_index(), item, lambda items: _run_group(grp, items))
     if out is None:
         return None
@@ -441,7 +504,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
     `video_path` / `video_data` (+ `duration`); `uncond_embeddings` (optional); `noisy_latents` or `generator`; for
     image-to-video `controlnet_images` or `condition_image_path_list` (either one turns SparseCtrl on; all examples or none);
     `motion_topk` overrides input_config.motion_topk for that example (one value for all the examples of a batch);
-    `motion_mask` (tensor or path) is that example's motion mask (default: the pipeline's / the yaml's `motion_mask_path`).
+    `motion_mask` (tensor or path) is that example's motion mask (default: the pipeline's / the yaml's `motion_mask_path`);
+    `motion_references` that example's further motion references (default: the pipeline's / the yaml's `motion_references`).
     Returns a list of V results, each what `sample_video(decode=...)` returns for that example.
 
     Host work (VAE posterior draw, extraction noise, condition-image VAE draw, CLIP, latent prior) runs per example in list
@@ -469,7 +533,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
                                               video_data=ex.get("video_data"), motion_topk=ex.get("motion_topk"))
             return [self.sample_video(eta=eta, generator=ex.get("generator"), noisy_latents=ex.get("noisy_latents"),
                                       add_controlnet=use_ctrl, text_embeddings=ex.get("text_embeddings"), decode=decode,
-                                      controlnet_images=ex.get("controlnet_images"), motion_mask=ex.get("motion_mask"))]
+                                      controlnet_images=ex.get("controlnet_images"), motion_mask=ex.get("motion_mask"),
+                                      motion_references=ex.get("motion_references"))]
         finally:
             for k, v in old.items():
                 setattr(cfg, k, v)
@@ -526,7 +591,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
     reps = smp.extract(torch.cat(vids, 0).half(), torch.cat(noises, 0).half(), torch.cat(unconds, 0).half(),
                        add_noise_step=step_t, ctrl=ext_ctrl, topk=topks[0])
     x = _packed_sample(self, lats, texts, reps, ctrls, eta=eta, generators=[ex.get("generator") for ex in examples],
-                       masks=[_motion_mask(self, ex.get("motion_mask"))[0] for ex in examples])
+                       masks=[_motion_mask(self, ex.get("motion_mask"))[0] for ex in examples],
+                       references=[_motion_references(self, ex.get("motion_references")) for ex in examples])
     if not decode:
         return [x[v:v + 1].clone() for v in range(V)]     # (a replayed step hands out the graph's static buffer: copies)
     return [self.decode_latents(x[v:v + 1]) for v in range(V)]
