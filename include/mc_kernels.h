@@ -320,6 +320,20 @@ int mc_cfg_ddim_step_batched_f16(const void* eps_c, const void* eps_u, int ld, c
                                  void* out, void* eps_out, float cfg, float sqrt_a_t, float sqrt_1m_a_t,
                                  float sqrt_a_prev, float sqrt_1m_a_prev, float score_coef, int V, int CL, int F, int HW,
                                  void* stream);
+/* Sliding context windows over a long video: F frames, windows of L <= 32 frames at stride S = L - overlap (1 <= S <= L),
+ * window w starts at min(w S, F - L) (the last one is clamped to the end), nW = ceil((F - L) / S) + 1 <= 32.
+ * mc_latent_windows_f16 gathers x [1, CL, F, H, W] into out [nW, CL, L, H, W].
+ * mc_cfg_ddim_step_windows_f16 is the update of the long latent from the windows' predictions: eps_c / eps_u
+ * [(w j y x), ld] window-major (w the window, j the frame inside it), score fp32 [nW, CL, L, H, W] (may be NULL), wt [L] fp32 frame weights on the device, x, out,
+ * eps_out (may be NULL) [1, CL, F, H, W].  Per element the windows that cover its frame are taken in ascending w with
+ * a_w = wt[f - s_w] / sum of those weights; eps = sum a_w (eps_c + cfg (eps_c - eps_u))_w and score = sum a_w score_w in
+ * fp32, then the update of mc_cfg_ddim_step_f16.  A frame covered by one window is bit-identical to
+ * mc_cfg_ddim_step_batched_f16 on that window's rows.  64-bit offsets, one writer per element. */
+int mc_latent_windows_f16(const void* x, void* out, int nW, int CL, int F, int L, int S, int HW, void* stream);
+int mc_cfg_ddim_step_windows_f16(const void* eps_c, const void* eps_u, int ld, const void* x, const float* score,
+                                 const float* wt, void* out, void* eps_out, float cfg, float sqrt_a_t, float sqrt_1m_a_t,
+                                 float sqrt_a_prev, float sqrt_1m_a_prev, float score_coef, int nW, int CL, int F, int L,
+                                 int S, int HW, void* stream);
 /* schedule_customized_step with every branch (motionclone_functions.py:285-409): prediction_type epsilon / sample /
  * v_prediction, clip_sample, use_clipped_model_output, eta > 0 with variance noise, the score term, return_middle.
  *   x0  = x0_s * sample + x0_m * model_output, clamped to [-clip, clip] if clip > 0;

@@ -412,6 +412,128 @@ __global__ void cfg_ddim_batched_kernel(const half_t* eps_c, const half_t* eps_u
     }
 }
 
+// ---- sliding context windows over a long video ---------------------------------------------------------------------------
+// F frames, windows of L frames at stride S: window w starts at min(w S, F - L) (the last one is clamped to the end, so
+// every window is full and every frame is covered); nW = ceil((F - L) / S) + 1.
+__host__ __device__ inline int ctx_window_start(int w, int F, int L, int S) {
+    const long s = (long)w * S;
+    return (int)(s < (long)(F - L) ? s : (long)(F - L));
+}
+
+// normalised weight of a covering window; a frame covered by ONE window has Z == g (0 + g) and gets exactly 1.0, whatever
+// the division is compiled to
+__device__ __forceinline__ float ctx_weight(float g, float Z) { return g == Z ? 1.0f : g / Z; }
+
+// cfg_ddim_elem in two parts, for an eps and a score value that are blends: the CFG combination of one window's pair, and
+// the update of one element from its eps (before the score term) and its score value (read only when has_score).
+// A frame covered by one window must come out bit-identical to cfg_ddim_kernel / cfg_ddim_elem.  Under -ffast-math the
+// compiler is free to choose, per kernel, which product of  a_prev x0 + b e2  is rounded before the final fma and how the
+// division is folded, and it chose differently here than there.  So the device build spells out the one sequence that every
+// existing update kernel compiles to (read off their ISA):  eps = fma(ec - eu, cfg, ec);  e2 = fma(-score, coef, eps);
+// out = fma(b, e2, (a_prev * rcp(sqrt_a_t)) * fma(-eps, sqrt(1 - a_t), x)).  The host simulator compiles both without
+// fast-math, so there the plain expressions already agree.  tests/test_context_kernels.py holds the two together.
+#ifdef MC_EMU
+__device__ __forceinline__ float cfg_ddim_x0_scale(const DdimCoef& k) { return k.sqrt_a_prev; }
+__device__ __forceinline__ float cfg_eps(float ec, float eu, const DdimCoef& k) { return ec + k.cfg * (ec - eu); }
+__device__ __forceinline__ float cfg_ddim_value(float eps, bool has_score, float sv, float xv, float, const DdimCoef& k) {
+    float x0 = (xv - k.sqrt_1m_a_t * eps) / k.sqrt_a_t;     // uses the un-guided eps (quirk A12)
+    float e2 = eps;
+    if (has_score) e2 -= k.score_coef * sv;
+    return k.sqrt_a_prev * x0 + k.sqrt_1m_a_prev * e2;
+}
+#else
+__device__ __forceinline__ float cfg_ddim_x0_scale(const DdimCoef& k) { return k.sqrt_a_prev * __builtin_amdgcn_rcpf(k.sqrt_a_t); }
+__device__ __forceinline__ float cfg_eps(float ec, float eu, const DdimCoef& k) { return __builtin_fmaf(ec - eu, k.cfg, ec); }
+__device__ __forceinline__ float cfg_ddim_value(float eps, bool has_score, float sv, float xv, float x0_scale,
+                                                const DdimCoef& k) {
+    const float num = __builtin_fmaf(-eps, k.sqrt_1m_a_t, xv);      // sqrt(a_t) x0, from the un-guided eps (quirk A12)
+    const float e2 = has_score ? __builtin_fmaf(-sv, k.score_coef, eps) : eps;
+    const float t = x0_scale * num;
+    return __builtin_fmaf(k.sqrt_1m_a_prev, e2, t);
+}
+#endif
+// x0_scale = cfg_ddim_x0_scale(k), formed once per thread
+__device__ __forceinline__ void cfg_ddim_apply(float eps, bool has_score, float sv, const half_t* x, half_t* out,
+                                               half_t* eps_out, size_t idx, float x0_scale, const DdimCoef& k) {
+    out[idx] = to_half(cfg_ddim_value(eps, has_score, sv, (float)x[idx], x0_scale, k));
+    if (eps_out) eps_out[idx] = to_half(eps);
+}
+
+// x [1, CL, F, HW] -> out [nW, CL, L, HW]: out[w, c, j, p] = x[c, s_w + j, p]
+__global__ void latent_windows_kernel(const half_t* x, half_t* out, int nW, int CL, int F, int L, int S, int HW) {
+    const long total = (long)nW * CL * L * HW;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long p = idx % HW;
+        long r = idx / HW;
+        const int j = (int)(r % L);
+        r /= L;
+        const int c = (int)(r % CL);
+        const int w = (int)(r / CL);
+        const int f = ctx_window_start(w, F, L, S) + j;
+        out[idx] = x[((size_t)c * F + (size_t)f) * HW + (size_t)p];
+    }
+}
+
+// The CFG + DDIM update of the LONG latent from the nW windows' predictions.  eps_c / eps_u [(w j y x), ld] window-major (the
+// token rows of the packed forward on the gathered windows), score fp32 [nW, CL, L, HW] or NULL, wt [L] the frame weights
+// inside a window; x, out, eps_out [1, CL, F, HW].  One thread per token (f, p) of the long latent: the windows that cover f
+// are visited in ascending w, Z = sum of wt[f - s_w], a_w = wt[f - s_w] / Z, eps = sum a_w eps_w and score = sum a_w score_w
+// (fp32, from 0), then cfg_ddim_apply (the batched kernel's arithmetic).  A frame covered by one window has a_w == 1.0 exactly and is
+// bit-identical to the batched update on that window's rows.  No atomics: a long-latent element has exactly one writer.
+template <bool VEC4>
+__global__ void cfg_ddim_windows_kernel(const half_t* eps_c, const half_t* eps_u, int ld, const half_t* x,
+                                        const float* score, const float* wt, half_t* out, half_t* eps_out, DdimCoef k,
+                                        int nW, int CL, int F, int L, int S, int HW) {
+    const long tokens = (long)F * HW;
+    const size_t plane = (size_t)F * HW;          // channel stride of the long latent
+    const size_t wplane = (size_t)L * HW;         // channel stride inside a window's score
+    const float x0_scale = cfg_ddim_x0_scale(k);
+    for (long tok = (long)blockIdx.x * blockDim.x + threadIdx.x; tok < tokens;
+         tok += (long)gridDim.x * blockDim.x) {
+        const long p = tok % HW;
+        const int f = (int)(tok / HW);
+        float Z = 0.f;
+        for (int w = 0; w < nW; ++w) {
+            const int j = f - ctx_window_start(w, F, L, S);
+            if (j >= 0 && j < L) Z += wt[j];
+        }
+        float eps[VEC4 ? 4 : 1], sc[VEC4 ? 4 : 1];
+        if (VEC4) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) eps[c] = sc[c] = 0.f;
+            for (int w = 0; w < nW; ++w) {
+                const int j = f - ctx_window_start(w, F, L, S);
+                if (j < 0 || j >= L) continue;
+                const float a = ctx_weight(wt[j], Z);
+                const size_t row = ((size_t)w * L + (size_t)j) * HW + (size_t)p;
+                const half4_t c4 = ld4(eps_c + row * ld), u4 = ld4(eps_u + row * ld);
+                const size_t so = (((size_t)w * CL) * L + (size_t)j) * HW + (size_t)p;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    eps[c] += a * cfg_eps((float)c4[c], (float)u4[c], k);
+                    if (score) sc[c] += a * score[so + c * wplane];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                cfg_ddim_apply(eps[c], score != nullptr, sc[c], x, out, eps_out, (size_t)tok + c * plane, x0_scale, k);
+        } else {
+            for (int c = 0; c < CL; ++c) {
+                eps[0] = sc[0] = 0.f;
+                for (int w = 0; w < nW; ++w) {
+                    const int j = f - ctx_window_start(w, F, L, S);
+                    if (j < 0 || j >= L) continue;
+                    const float a = ctx_weight(wt[j], Z);
+                    const size_t row = ((size_t)w * L + (size_t)j) * HW + (size_t)p;
+                    eps[0] += a * cfg_eps((float)eps_c[row * ld + c], (float)eps_u[row * ld + c], k);
+                    if (score) sc[0] += a * score[(((size_t)w * CL + c) * L + (size_t)j) * HW + (size_t)p];
+                }
+                cfg_ddim_apply(eps[0], score != nullptr, sc[0], x, out, eps_out, (size_t)tok + c * plane, x0_scale, k);
+            }
+        }
+    }
+}
+
 // schedule_customized_step in full (motionclone_functions.py:285-409): every branch is an affine map of
 // (sample, model_output, score, variance_noise), same [B, C, F, H, W] layout for all operands
 struct DdimGeneral {
@@ -540,6 +662,38 @@ extern "C" int mc_cfg_ddim_step_batched_f16(const void* eps_c, const void* eps_u
         MC_LAUNCH(cfg_ddim_batched_kernel<false>, dim3(ew_blocks(tokens)), dim3(256), 0, (hipStream_t)stream,
                   (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, (half_t*)out,
                   (half_t*)eps_out, k, V, CL, F, HW);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+static inline bool ctx_shape_ok(int nW, int F, int L, int S) {
+    if (L < 1 || L > 32 || S < 1 || S > L || F < L || nW < 1 || nW > 32) return false;
+    return nW == (F - L + S - 1) / S + 1;
+}
+
+extern "C" int mc_latent_windows_f16(const void* x, void* out, int nW, int CL, int F, int L, int S, int HW, void* stream) {
+    if (!x || !out || CL <= 0 || HW <= 0 || !ctx_shape_ok(nW, F, L, S)) return MC_ERR_SHAPE;
+    MC_LAUNCH(latent_windows_kernel, dim3(ew_blocks((long)nW * CL * L * HW)), dim3(256), 0, (hipStream_t)stream,
+              (const half_t*)x, (half_t*)out, nW, CL, F, L, S, HW);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+extern "C" int mc_cfg_ddim_step_windows_f16(const void* eps_c, const void* eps_u, int ld, const void* x,
+                                            const float* score, const float* wt, void* out, void* eps_out, float cfg,
+                                            float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev,
+                                            float score_coef, int nW, int CL, int F, int L, int S, int HW, void* stream) {
+    if (!eps_c || !eps_u || !x || !wt || !out || CL <= 0 || HW <= 0 || ld < CL || !ctx_shape_ok(nW, F, L, S))
+        return MC_ERR_SHAPE;
+    DdimCoef k{cfg, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev, score_coef};
+    const long tokens = (long)F * HW;
+    const bool vec4 = CL == 4 && ld % 4 == 0 && ((uintptr_t)eps_c | (uintptr_t)eps_u) % 8 == 0;
+    if (vec4)
+        MC_LAUNCH(cfg_ddim_windows_kernel<true>, dim3(ew_blocks(tokens)), dim3(256), 0, (hipStream_t)stream,
+                  (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, wt, (half_t*)out,
+                  (half_t*)eps_out, k, nW, CL, F, L, S, HW);
+    else
+        MC_LAUNCH(cfg_ddim_windows_kernel<false>, dim3(ew_blocks(tokens)), dim3(256), 0, (hipStream_t)stream,
+                  (const half_t*)eps_c, (const half_t*)eps_u, ld, (const half_t*)x, score, wt, (half_t*)out,
+                  (half_t*)eps_out, k, nW, CL, F, L, S, HW);
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
 }
 

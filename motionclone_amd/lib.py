@@ -76,6 +76,8 @@ SIGNATURES = {
     "mc_silu_f16": [P, P, L, P],
     "mc_cfg_ddim_step_f16": [P, P, I, P, P, P, P, F, F, F, F, F, F, I, I, I, P],
     "mc_cfg_ddim_step_batched_f16": [P, P, I, P, P, P, P, F, F, F, F, F, F, I, I, I, I, P],
+    "mc_latent_windows_f16": [P, P, I, I, I, I, I, I, P],
+    "mc_cfg_ddim_step_windows_f16": [P, P, I, P, P, P, P, P, F, F, F, F, F, F, I, I, I, I, I, I, P],
     "mc_ddim_step_general_f16": [P, P, P, P, P, P, P, L, F, F, F, F, F, I, F, F, F, F, F, F, P],
 }
 

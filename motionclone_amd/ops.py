@@ -787,3 +787,87 @@ def cfg_ddim_step(eps_c, eps_u, x, score, cfg, a_t, a_prev, score_coef, want_eps
         lib.call("mc_cfg_ddim_step_batched_f16", _p(eps_c), _p(eps_u), _ld(eps_c), _p(x), _p(score), _p(out), _p(eps_out),
                  *coefs, V, CL, F, H * W, _stream(x))
     return (out, eps_out) if want_eps else out
+
+
+# ---- sliding context windows over a long video ---------------------------------------------------------------------------
+CONTEXT_MAX_LENGTH = 32      # a window is one ordinary video for the temporal kernels (csrc/temporal.hip: F <= 32)
+CONTEXT_MAX_WINDOWS = 32
+CONTEXT_WEIGHTS = ("triangular", "uniform")
+
+
+def context_windows(F, L, overlap):
+    """THE window rule (the kernels restate it, mc_kernels.h): the first frames of the windows of L frames at stride
+    S = L - overlap over a video of F frames.  F <= L: no windows ([]), the ordinary path runs.  Otherwise
+    nW = ceil((F - L) / S) + 1 windows, window w starting at min(w S, F - L): the last one is clamped to the end, so every
+    window is full and every frame is covered."""
+    F, L, overlap = int(F), int(L), int(overlap)
+    if not 1 <= L <= CONTEXT_MAX_LENGTH:
+        raise ValueError("context windows: length L = %d outside 1 .. %d" % (L, CONTEXT_MAX_LENGTH))
+    if not 0 <= overlap < L:
+        raise ValueError("context windows: overlap %d outside 0 .. L - 1 = %d" % (overlap, L - 1))
+    if F < 1:
+        raise ValueError("context windows: %d frames" % F)
+    if F <= L:
+        return []
+    S = L - overlap
+    nW = -(-(F - L) // S) + 1
+    if nW > CONTEXT_MAX_WINDOWS:
+        raise ValueError("context windows: F = %d frames with L = %d, overlap %d need %d windows, at most %d are supported"
+                         % (F, L, overlap, nW, CONTEXT_MAX_WINDOWS))
+    return [min(w * S, F - L) for w in range(nW)]
+
+
+def context_weights(L, kind="triangular", device=None):
+    """the frame weights inside a window, fp32 [L]: 'uniform' (all 1) or 'triangular' (min(j + 1, L - j))"""
+    if kind not in CONTEXT_WEIGHTS:
+        raise ValueError("context windows: weights %r, expected one of %s" % (kind, list(CONTEXT_WEIGHTS)))
+    w = [1.0] * L if kind == "uniform" else [float(min(j + 1, L - j)) for j in range(L)]
+    return torch.tensor(w, dtype=torch.float32, device=device)
+
+
+def latent_windows(x, L, overlap):
+    """x [1, CL, F, H, W] fp16 -> the windows [nW, CL, L, H, W] of `context_windows(F, L, overlap)` (mc_latent_windows_f16)"""
+    if x.dim() != 5 or x.shape[0] != 1:
+        raise ValueError("latent_windows: one long video [1, CL, F, H, W] is expected, got %s" % (tuple(x.shape),))
+    _, CL, F, H, W = x.shape
+    starts = context_windows(F, L, overlap)
+    if not starts:
+        raise ValueError("latent_windows: F = %d frames fit one window of L = %d, there is nothing to gather" % (F, L))
+    x = _f16(x).contiguous()
+    out = torch.empty((len(starts), CL, L, H, W), dtype=x.dtype, device=x.device)
+    lib.call("mc_latent_windows_f16", _p(x), _p(out), len(starts), CL, F, int(L), int(L) - int(overlap), H * W, _stream(x))
+    return out
+
+
+def cfg_ddim_step_windows(eps_c, eps_u, x, score, wt, L, overlap, cfg, a_t, a_prev, score_coef, want_eps=False, sigma=0.0):
+    """`cfg_ddim_step` of a LONG latent x [1, CL, F, H, W] from the predictions of its context windows: eps_* token matrices
+    [(w j y x), ld] window-major (the rows of the packed forward on `latent_windows(x, L, overlap)`), score fp32
+    [nW, CL, L, H, W] or None, wt = `context_weights(L, ...)` on x's device.  Every window's whole update (guidance term
+    included) is averaged per frame with the normalised weights of the windows that cover it; a frame covered by one window
+    is bit-identical to `cfg_ddim_step` on that window's rows.  ONE launch of mc_cfg_ddim_step_windows_f16."""
+    if x.dim() != 5 or x.shape[0] != 1:
+        raise ValueError("cfg_ddim_step_windows: one long video [1, CL, F, H, W] is expected, got %s" % (tuple(x.shape),))
+    _, CL, F, H, W = x.shape
+    starts = context_windows(F, L, overlap)
+    nW = len(starts)
+    if nW == 0:
+        raise ValueError("cfg_ddim_step_windows: F = %d frames fit one window of L = %d (use cfg_ddim_step)" % (F, L))
+    rows = nW * int(L) * H * W
+    if eps_c.shape[0] != rows or eps_u.shape[0] != rows:
+        raise ValueError("cfg_ddim_step_windows: %d windows of %d tokens need eps rows [(w j y x)] = %d, got %d / %d" % (
+            nW, int(L) * H * W, rows, eps_c.shape[0], eps_u.shape[0]))
+    if score is not None and tuple(score.shape) != (nW, CL, int(L), H, W):
+        raise ValueError("cfg_ddim_step_windows: score %s, expected %s" % (tuple(score.shape), (nW, CL, int(L), H, W)))
+    if tuple(wt.shape) != (int(L),) or wt.device != x.device:
+        raise ValueError("cfg_ddim_step_windows: frame weights %s on %s, expected [%d] on %s" % (tuple(wt.shape), wt.device, int(L), x.device))
+    x = _f16(x).contiguous()
+    out = torch.empty_like(x)
+    eps_out = torch.empty_like(x) if want_eps else None
+    if score is not None:
+        score = _f32(score.contiguous())
+    assert _ld(eps_c) == _ld(eps_u)
+    coefs = (float(cfg), float(a_t) ** 0.5, float(1.0 - a_t) ** 0.5, float(a_prev) ** 0.5,
+             max(float(1.0 - a_prev) - float(sigma) ** 2, 0.0) ** 0.5, float(score_coef))
+    lib.call("mc_cfg_ddim_step_windows_f16", _p(_f16(eps_c)), _p(_f16(eps_u)), _ld(eps_c), _p(x), _p(score), _p(_f32(wt)),
+             _p(out), _p(eps_out), *coefs, nW, CL, F, int(L), int(L) - int(overlap), H * W, _stream(x))
+    return (out, eps_out) if want_eps else out

@@ -62,6 +62,7 @@ class MotionCloneSampler:
         self.score_gs = float(score_guidance_scale)
         self._graphs = None      # step index -> (hipGraph, static input, static output); see enable_graphs()
         self._graph_pool = None
+        self._ctx_wt = {}         # (L, weights) -> the frame weights of a context window on the device (made outside any capture)
         self._warm_kinds = set()  # {(guided?, SparseCtrl?, latent shape, text shape, GEMM share)} kinds of step that already ran once eagerly on this sampler
 
     def _gemm_share(self):
@@ -92,13 +93,66 @@ class MotionCloneSampler:
         a = float(self.acp[int(t)])
         return (a ** 0.5 * x0.float() + (1 - a) ** 0.5 * noise.float()).to(x0.dtype)
 
+    def windows(self, context, frames):
+        """Sliding context windows of a long video.  `context` = dict(length, overlap = length // 4, weights = 'triangular')
+        or None; `frames` = the video's frame count F.  None when no context is set or F <= length (the ordinary path runs,
+        unchanged); otherwise (L, overlap, weights, starts, wt): the window rule of ops.context_windows and the frame weights
+        on the device.  A long video is then ONE latent [1, 4, F, H, W] whose windows run as a packed batch of nW videos."""
+        if context is None:
+            return None
+        if len(context) == 5 and not isinstance(context, dict):
+            return context      # already resolved
+        unknown = set(context) - {"length", "overlap", "weights"}
+        if unknown or "length" not in context:
+            raise ValueError("context: dict(length, overlap, weights) is expected, got keys %s" % sorted(context))
+        L = int(context["length"])
+        overlap = context.get("overlap")
+        overlap = L // 4 if overlap is None else int(overlap)
+        weights = context.get("weights") or "triangular"
+        if weights not in ops.CONTEXT_WEIGHTS:
+            raise ValueError("context: weights %r, expected one of %s" % (weights, list(ops.CONTEXT_WEIGHTS)))
+        starts = ops.context_windows(frames, L, overlap)
+        if not starts:
+            return None
+        wt = self._ctx_wt.get((L, weights))
+        if wt is None:
+            wt = self._ctx_wt[(L, weights)] = ops.context_weights(L, weights, device=self.dev)
+        return (L, overlap, weights, tuple(starts), wt)
+
+    @staticmethod
+    def window_masks(mask, win, frames):
+        """a motion mask of a long video, [F, H', W'] or [H', W'], as the list of the windows' masks (the V > 1 mask list)"""
+        if mask is None:
+            return None
+        if isinstance(mask, (list, tuple)):
+            raise ValueError("motion mask: with a context one mask [F, H', W'] or [H', W'] of the long video is expected, not a list")
+        mask = torch.as_tensor(mask)
+        if mask.dim() == 3:
+            if mask.shape[0] != int(frames):
+                raise ValueError("motion mask: shape %s holds %d frames, the run has %d" % (tuple(mask.shape), mask.shape[0], int(frames)))
+            return [mask[s:s + win[0]] for s in win[3]]
+        return [mask] * len(win[3])
+
     @ops.scoped
-    def extract(self, video_latents, noise, uncond_text, add_noise_step=400, ctrl=None, topk=1):
+    def extract(self, video_latents, noise, uncond_text, add_noise_step=400, ctrl=None, topk=1, context=None):
         """ctrl = dict(cond, mask, scale) runs the SparseCtrl encoder first (motionclone_functions.py:46-72).
         V > 1 reference videos (video_latents / noise [V, 4, F, H, W], uncond_text [V, n, dim] or [1, n, dim] for all of them,
         ctrl batched as in `_step_eager`): ONE partial forward, one top-k launch per hooked attention; a list of V
         representations comes back.  `topk`: the sparsity of the representation, values / indices [BN, heads, F, topk]
-        (1 = the reference's producer; the steps infer it from the representation they are given)."""
+        (1 = the reference's producer; the steps infer it from the representation they are given).
+        `context` (see `windows`) with a reference longer than its length: ONE noise tensor for the long latent
+        [1, 4, F, H, W], the windows of the noisy latent are gathered and run as the V = nW extraction; a list of nW
+        representations, one per window, comes back."""
+        win = self.windows(context, video_latents.shape[2])
+        if win is not None:
+            if ctrl is not None:
+                raise NotImplementedError("context: SparseCtrl (ctrl) with context windows is not supported")
+            if video_latents.shape[0] != 1 or uncond_text.shape[0] != 1:
+                raise ValueError("context: one long reference video [1, 4, F, H, W] with uncond_text [1, n, dim] is expected, got "
+                                 "%s / %s" % (tuple(video_latents.shape), tuple(uncond_text.shape)))
+            noisy = ops.latent_windows(self.add_noise(add_noise_step, video_latents, noise), win[0], win[1])
+            return self.engine.extract_representation(noisy, add_noise_step, uncond_text.expand(len(win[3]), -1, -1).contiguous(),
+                                                      topk=topk)
         V = video_latents.shape[0]
         if uncond_text.shape[0] != V:
             if uncond_text.shape[0] != 1:
@@ -129,7 +183,7 @@ class MotionCloneSampler:
         self._graphs = {}
         return self
 
-    def _graphed_step(self, latents, i, text, rep_dev, ctrl):
+    def _graphed_step(self, latents, i, text, rep_dev, ctrl, win=None):
         """One hipGraph per (step index, shapes).  Everything that changes between videos - latents, text embeddings, the
         motion representation with its region weights (a new mask of the same shape is a copy, not a capture), the SparseCtrl
         condition - enters through static buffers that are refreshed by copies before
@@ -140,7 +194,8 @@ class MotionCloneSampler:
         # yet other kernels.  Other references of the same shapes are a copy into the static buffers, not a capture.
         rsig = tuple((k, tuple(v[0].shape), len(v) == 3, len(v) == 3 and v[2].dim() == 3) for k, v in rep_dev.items()) if guided else ()
         csig = None if ctrl is None else (tuple(ctrl["cond"].shape), tuple(ctrl["mask"].shape), float(ctrl.get("scale", 1.0)))
-        key = (i, tuple(latents.shape), tuple(text.shape), rsig, csig, self._gemm_share())   # the GEMM geometry is baked in
+        wsig = None if win is None else win[:3]       # context windows: the long shape plus (length, overlap, weights)
+        key = (i, tuple(latents.shape), tuple(text.shape), rsig, csig, self._gemm_share(), wsig)   # the GEMM geometry is baked in
         ent = self._graphs.get(key)
         if ent is None:
             from . import lanes
@@ -157,18 +212,18 @@ class MotionCloneSampler:
                 # the graph key without the step index: a new resolution, batch size or GEMM share setting touches kernels and
                 # GEMM geometries (e.g. the two-workgroup tiles, chosen only for share 0) that have not run eagerly yet
                 # ... and the representation's shapes: another top-k K means other read-out / seed kernels
-                kind = (guided, ctrl is not None, tuple(latents.shape), tuple(text.shape), self._gemm_share(), rsig)
+                kind = (guided, ctrl is not None, tuple(latents.shape), tuple(text.shape), self._gemm_share(), rsig, wsig)
                 if kind not in self._warm_kinds:
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(side):
-                        self._step_eager(s_lat, i, s_text, s_rep, None, s_ctrl)
+                        self._step_eager(s_lat, i, s_text, s_rep, None, s_ctrl, context=win)
                     torch.cuda.current_stream().wait_stream(side)
                     self._warm_kinds.add(kind)
                 graph = torch.cuda.CUDAGraph()
                 # thread_local: other host threads (launcher lanes) keep allocating / launching while this one captures
                 with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
-                    s_out = self._step_eager(s_lat, i, s_text, s_rep, None, s_ctrl)
+                    s_out = self._step_eager(s_lat, i, s_text, s_rep, None, s_ctrl, context=win)
                 if self._graph_pool is None:
                     self._graph_pool = graph.pool()
             self._graphs[key] = (graph, s_lat, s_text, s_rep, s_ctrl, s_out)
@@ -189,21 +244,24 @@ class MotionCloneSampler:
         graph.replay()
         return s_out
 
-    def step(self, latents, i, text, rep_dev, aux=None, ctrl=None, eta=0.0, generator=None, variance_noise=None):
+    def step(self, latents, i, text, rep_dev, aux=None, ctrl=None, eta=0.0, generator=None, variance_noise=None, context=None):
         """single_step_video (motionclone_functions.py:173-257): text = [uncond, cond] embeddings [2, n, dim];
         ctrl = dict(cond, mask, scale) enables the SparseCtrl pass of :176-197 (one B=2 encoder run per step);
         eta / generator / variance_noise = the `extra_step_kwargs` handed on to schedule_customized_step (:241,255):
         eta > 0 adds eta * sigma_t * noise, drawn like randn_tensor unless given (never captured in a graph).
         ALIASING: with `enable_graphs()` a replayed step returns the graph's static output buffer - valid until the same
         step index is replayed again (the next video on this sampler); callers that keep a result across videos clone it
-        (the drop-in `single_step_video` / `sample_video` do)."""
+        (the drop-in `single_step_video` / `sample_video` do).
+        `context` (see `windows`) with more frames than its length: `latents` is the long latent [1, 4, F, H, W], `rep_dev`
+        the prepared list of the nW windows' representations, and the long latent of the next step comes back."""
+        win = self.windows(context, latents.shape[2])
         if eta:
             if variance_noise is not None and generator is not None:
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
                                  " `variance_noise` stays `None`.")
             t, a_t, a_prev = self._alphas(i)
             sigma = float(eta) * max((1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev), 0.0) ** 0.5
-            prev = self._step_eager(latents, i, text, rep_dev, aux, ctrl, sigma)
+            prev = self._step_eager(latents, i, text, rep_dev, aux, ctrl, sigma, context=win)
             if variance_noise is None:
                 gdev = generator.device if generator is not None else latents.device
                 variance_noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=latents.dtype).to(latents.device)
@@ -211,13 +269,13 @@ class MotionCloneSampler:
             ops.add(flat, variance_noise.to(prev.dtype).contiguous().reshape(flat.shape), out=flat, sa=1.0, sb=sigma)
             return prev
         if self._graphs is not None and aux is None and latents.is_cuda:
-            out = self._graphed_step(latents, i, text, rep_dev, ctrl)
+            out = self._graphed_step(latents, i, text, rep_dev, ctrl, win)
             if out is not None:
                 return out
-        return self._step_eager(latents, i, text, rep_dev, aux, ctrl)
+        return self._step_eager(latents, i, text, rep_dev, aux, ctrl, context=win)
 
     @ops.scoped
-    def _step_eager(self, latents, i, text, rep_dev, aux=None, ctrl=None, sigma=0.0):
+    def _step_eager(self, latents, i, text, rep_dev, aux=None, ctrl=None, sigma=0.0, context=None):
         """latents [V, 4, F, H, W]; text [2 V, n, dim] ordered [u_1 .. u_V | c_1 .. c_V] (V = 1: [uncond, cond], the reference's
         layout); rep_dev: engine.prepare_representation of the V representations (a list for V > 1), its entries two-tuples or,
         with a motion mask, three-tuples whose last element is the row weights [BN, F], with several references per video
@@ -226,9 +284,24 @@ class MotionCloneSampler:
         reduction crosses the batch - but the GEMM tile / split-K choice follows the larger row count, so results agree
         with the one-video path to fp16 rounding, not bit for bit.  ctrl: `cond` [V, ...] / `mask` [V, 1, ...] carry one
         SparseCtrl condition per video ([1, ...]: the same one for all); with batch_guided=False the uncond forward and the
-        differentiated cond forward each run on V elements with their halves of the encoder's residuals."""
+        differentiated cond forward each run on V elements with their halves of the encoder's residuals.
+        `context` with windows active (see `windows`): latents is ONE long video [1, 4, F, H, W] and text [uncond, cond]; its nW
+        windows are gathered and run as the packed batch above (text [u] * nW + [c] * nW, rep_dev the nW windows'
+        representations), and ONE windowed update blends the windows' updates per frame into the long latent of the next step
+        (`aux` then holds the per-window eps_u / eps_c / grad of the packed run)."""
         from .engine import split_residuals
         eng = self.engine
+        win = self.windows(context, latents.shape[2])
+        x_long = None
+        if win is not None:
+            if ctrl is not None:
+                raise NotImplementedError("context: SparseCtrl (ctrl) with context windows is not supported")
+            if latents.shape[0] != 1 or text.shape[0] != 2:
+                raise ValueError("context: one long video [1, 4, F, H, W] with text [uncond, cond] is expected, got %s / %s" % (
+                    tuple(latents.shape), tuple(text.shape)))
+            nW = len(win[3])
+            x_long, latents = latents, ops.latent_windows(latents, win[0], win[1])
+            text = torch.cat([text[0:1].expand(nW, -1, -1), text[1:2].expand(nW, -1, -1)], 0)
         V = latents.shape[0]
         if text.shape[0] != 2 * V:
             raise ValueError("text must hold [uncond x V | cond x V] embeddings: %s for %d videos" % (tuple(text.shape), V))
@@ -240,6 +313,9 @@ class MotionCloneSampler:
             down, mid = self.controlnet.forward(shape2, t, text, ctrl["cond"], ctrl["mask"], ctrl.get("scale", 1.0))
 
         def update(eps_c, eps_u, grad, coef):     # one launch for the V videos (V = 1: the one-video entry, as ever)
+            if win is not None:                   # ... or for the long latent, from its windows' predictions
+                return ops.cfg_ddim_step_windows(eps_c, eps_u, x_long, grad, win[4], win[0], win[1], self.cfg_scale, a_t, a_prev,
+                                                 coef, sigma=sigma)
             return ops.cfg_ddim_step(eps_c, eps_u, latents, grad, self.cfg_scale, a_t, a_prev, coef, sigma=sigma)
         if i < self.G:
             w = self.weight * self.guidance_factor(i)
@@ -270,13 +346,32 @@ class MotionCloneSampler:
             aux.update(eps_u=eps2[:T1], eps_c=eps2[T1:])
         return update(eps2[T1:], eps2[:T1], None, 0.0)
 
-    def sample(self, latents, text, rep, progress=None, ctrl=None, mask=None, mask_normalize=False, references=None):
+    def prepare_windows(self, rep, win, frames, mask=None, mask_normalize=False, grid=None):
+        """the representations of the nW windows of a long video (what `extract` with a context returns) as the packed batch's
+        `rep_dev`; a motion mask of the long video is sliced per window"""
+        if not isinstance(rep, (list, tuple)) or len(rep) != len(win[3]):
+            raise ValueError("context: %d windows need a list of %d motion representations (extract with the same context), got %s"
+                             % (len(win[3]), len(win[3]), "%d" % len(rep) if isinstance(rep, (list, tuple)) else type(rep).__name__))
+        return self.engine.prepare_representation(list(rep), frames=win[0], mask=self.window_masks(mask, win, frames),
+                                                  mask_normalize=mask_normalize, grid=grid)
+
+    def sample(self, latents, text, rep, progress=None, ctrl=None, mask=None, mask_normalize=False, references=None, context=None):
         """`mask`: a motion mask (a list with None entries for V > 1), `references`: further motion references of the video
-        (a list of such lists with None entries for V > 1), see engine.prepare_representation"""
-        rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2], mask=mask, mask_normalize=mask_normalize,
-                                                     grid=tuple(latents.shape[3:]), references=references)
+        (a list of such lists with None entries for V > 1), see engine.prepare_representation.
+        `context` (see `windows`) with more frames than its length: `latents` is one long video, `rep` the list of its windows'
+        representations, `mask` one mask [F, H', W'] or [H', W'] of the long video."""
+        win = self.windows(context, latents.shape[2])
+        if win is not None:
+            if references is not None:
+                raise NotImplementedError("context: motion composition (references) with context windows is not supported")
+            if ctrl is not None:
+                raise NotImplementedError("context: SparseCtrl (ctrl) with context windows is not supported")
+            rep_dev = self.prepare_windows(rep, win, latents.shape[2], mask, mask_normalize, tuple(latents.shape[3:]))
+        else:
+            rep_dev = self.engine.prepare_representation(rep, frames=latents.shape[2], mask=mask, mask_normalize=mask_normalize,
+                                                         grid=tuple(latents.shape[3:]), references=references)
         for i in range(len(self.timesteps)):
-            latents = self.step(latents, i, text, rep_dev, ctrl=ctrl)
+            latents = self.step(latents, i, text, rep_dev, ctrl=ctrl, context=win)
             if progress is not None:
                 progress(i)
         return latents

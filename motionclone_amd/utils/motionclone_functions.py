@@ -161,6 +161,53 @@ def _motion_references(pipe, override=None):
     return out
 
 
+def _context(cfg, frames):
+    """Sliding context windows of a long video (sampler.MotionCloneSampler.windows): the optional inference-yaml keys
+    `context_length` (L <= 32), `context_overlap` (default L // 4) and `context_weights` ('triangular', the default, or
+    'uniform').  -> (the sampler's `context` dict, the windows' first frames), or (None, []) when `context_length` is absent or
+    the `frames` of the run fit one window: every path is then as without the keys.  `video_length` may exceed 32 with them."""
+    L = getattr(cfg, "context_length", None)
+    if L is None:
+        for k in ("context_overlap", "context_weights"):
+            if getattr(cfg, k, None) is not None:
+                raise ValueError("%s is set without context_length" % k)
+        return None, []
+    L = int(L)
+    ov = getattr(cfg, "context_overlap", None)
+    ctx = dict(length=L, overlap=L // 4 if ov is None else int(ov), weights=getattr(cfg, "context_weights", None) or "triangular")
+    if ctx["weights"] not in ops.CONTEXT_WEIGHTS:
+        raise ValueError("context_weights: %r, expected one of %s" % (ctx["weights"], list(ops.CONTEXT_WEIGHTS)))
+    starts = ops.context_windows(frames, L, ctx["overlap"])
+    return (ctx, starts) if starts else (None, [])
+
+
+def _window_representations(rep, ctx, frames, nW):
+    """a representation written by obtain_motion_representation under a context ({module: [values, indices]} with the windows
+    folded window-major into the row axis, plus "motion_context") -> the list of the nW windows' representations; a file that
+    was extracted for another video length / context, or without one, is refused"""
+    want = dict(frames=int(frames), length=ctx["length"], overlap=ctx["overlap"])
+    mc = rep.get("motion_context") if hasattr(rep, "get") else None
+    if mc is None:
+        raise ValueError("context_length: the motion representation carries no motion_context entry - it was extracted without "
+                         "context windows; the run needs %s (run obtain_motion_representation with the same yaml keys)" % want)
+    have = {k: int(mc[k]) for k in ("frames", "length", "overlap") if k in mc}
+    if have != want:
+        raise ValueError("context_length: the motion representation was extracted with motion_context %s, the run has %s"
+                         % (have, want))
+    out = [dict() for _ in range(nW)]
+    for name, ent in rep.items():
+        if name == "motion_context":
+            continue
+        val, idx = ent[0], ent[1]
+        if val.shape[0] % nW:
+            raise ValueError("context_length: motion representation %s has %d rows, no multiple of the %d windows"
+                             % (name, val.shape[0], nW))
+        n = val.shape[0] // nW
+        for w in range(nW):
+            out[w][name] = [val[w * n:(w + 1) * n], idx[w * n:(w + 1) * n]]
+    return out
+
+
 @torch.no_grad()
 def obtain_motion_representation(self, generator=None, motion_representation_path: str = None, duration=None,
                                  use_controlnet=False, video_latents=None, uncond_embeddings=None, video_data=None,
@@ -168,7 +215,10 @@ def obtain_motion_representation(self, generator=None, motion_representation_pat
     """:25-82.  `video_latents` / `uncond_embeddings` let synthetic inputs bypass decord / VAE / CLIP (`video_data`
     [F, 3, H, W] in [-1, 1]: the preprocessed frames, needed beside `video_latents` only by the pixel-condition ControlNet).
     `motion_topk` (default: input_config.motion_topk, absent = 1): top-k values / indices per attention row, saved in the
-    reference's layout with last dimension k."""
+    reference's layout with last dimension k.
+    With the yaml key `context_length` and a reference longer than it (`_context`): one noise tensor for the long latent, the
+    windows of the noisy latent run as one batch; the entries hold the windows folded window-major into the row axis
+    ([nW BN, heads, L, k]) and an entry "motion_context": {frames, length, overlap} names what they were extracted for."""
     cfg = self.input_config
     topk = _motion_topk(cfg, motion_topk)
     if video_latents is None:
@@ -182,6 +232,14 @@ def obtain_motion_representation(self, generator=None, motion_representation_pat
     step_t = int(cfg.add_noise_step)
     noise = torch.randn(video_latents.shape, generator=generator, device=video_latents.device, dtype=video_latents.dtype)
     noisy = self.add_noise(step_t, video_latents, noise)
+    ctx, starts = _context(cfg, video_latents.shape[2])
+    if starts:
+        if use_controlnet:
+            raise NotImplementedError("context_length: SparseCtrl (use_controlnet) with context windows is not supported")
+        if video_latents.shape[0] != 1:
+            raise ValueError("context_length: one long reference video [1, 4, F, H, W] is expected, got %s" % (tuple(video_latents.shape),))
+        noisy = ops.latent_windows(noisy.half(), ctx["length"], ctx["overlap"])
+        uncond_embeddings = uncond_embeddings[0:1].expand(len(starts), -1, -1)
     down_res = mid_res = None
     if use_controlnet:   # :46-72: condition = the reference video's own frames at image_index
         idx = cfg.image_index
@@ -213,9 +271,11 @@ def obtain_motion_representation(self, generator=None, motion_representation_pat
             else:
                 val, idx = ops.tattn_topk(r["qkv"][:, :C], r["qkv"][:, C:2 * C], g.B, g.F, g.hw, module.heads, r["d"], topk)
             rep[name] = [val, idx]   # topk(k) value / uint8 index (:79 with k = motion_topk)
+    meta = dict(motion_context=dict(frames=int(video_latents.shape[2]), length=ctx["length"], overlap=ctx["overlap"])) if starts else {}
     if motion_representation_path is not None:
         # the reference's on-disk format: {module name: [values fp16 [BN, heads, F, k], indices uint8 [...]]} (:79-81)
-        torch.save({k: [v.cpu(), i.cpu()] for k, (v, i) in rep.items()}, motion_representation_path)
+        torch.save(dict({k: [v.cpu(), i.cpu()] for k, (v, i) in rep.items()}, **meta), motion_representation_path)
+    rep.update(meta)
     self.motion_representation_path = motion_representation_path
     self.motion_representation_dict = rep
     return rep
@@ -264,6 +324,9 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
         raise ValueError("step_t %d is not scheduler.timesteps[%d] = %d" % (int(step_t), step_index,
                                                                             int(smp.timesteps[step_index])))
     ctrl = None
+    ctx, starts = _context(self.input_config, noisy_latents.shape[2])
+    if starts and getattr(self, "add_controlnet", False):
+        raise NotImplementedError("context_length: SparseCtrl (add_controlnet) with context windows is not supported")
     if getattr(self, "add_controlnet", False):   # :176-197: condition latents placed at image_index, mask = 1 there
         smp.controlnet = self.controlnet.engine()
         ci = self.controlnet_images.to(noisy_latents.device, torch.float16)
@@ -282,7 +345,18 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
     if (getattr(self, "_mc_rep_src", None) is not self.motion_representation_dict
             or getattr(self, "_mc_rep_mask", None) is not self._mc_mask
             or getattr(self, "_mc_rep_refs", None) is not self._mc_refs):
-        if self._mc_refs is not None:            # motion composition: merged with the example's own reference here, once per video
+        if starts:                               # a long video: the windows' representations as one packed batch, once per video
+            if self._mc_refs is not None:
+                raise NotImplementedError("context_length: motion_references with context windows is not supported")
+            F = noisy_latents.shape[2]
+            self._mc_rep_dev = smp.prepare_windows(_window_representations(self.motion_representation_dict, ctx, F, len(starts)),
+                                                   smp.windows(ctx, F), F, mask=mask, mask_normalize=mask_norm,
+                                                   grid=tuple(noisy_latents.shape[3:]))
+        elif "motion_context" in self.motion_representation_dict:
+            raise ValueError("the motion representation was extracted with motion_context %s, but this run of %d frames has no "
+                             "context windows (yaml key context_length)" % (dict(self.motion_representation_dict["motion_context"]),
+                                                                            noisy_latents.shape[2]))
+        elif self._mc_refs is not None:            # motion composition: merged with the example's own reference here, once per video
             self._mc_rep_dev = smp.engine.prepare_representation(self.motion_representation_dict, frames=noisy_latents.shape[2],
                                                                  mask=mask, mask_normalize=mask_norm,
                                                                  grid=tuple(noisy_latents.shape[3:]), references=self._mc_refs)
@@ -297,7 +371,7 @@ def single_step_video(self, noisy_latents, step_index, step_t, extra_step_kwargs
         self._mc_rep_refs = self._mc_refs
     kw = dict(extra_step_kwargs or {})      # prepare_extra_step_kwargs: eta / generator, handed to customized_step (:241,255)
     out = smp.step(noisy_latents.half(), step_index, self.text_embeddings.half(), self._mc_rep_dev, ctrl=ctrl,
-                   eta=float(kw.get("eta", 0.0) or 0.0), generator=kw.get("generator") if kw.get("eta") else None)
+                   eta=float(kw.get("eta", 0.0) or 0.0), generator=kw.get("generator") if kw.get("eta") else None, context=ctx)
     # a replayed step returns the graph's STATIC output buffer (sampler._graphed_step), which the next replay of the same
     # step index - the next video - overwrites; the reference API hands out fresh tensors, so the boundary copies (0.5 MiB)
     if smp._graphs is not None:
@@ -343,6 +417,9 @@ def sample_video(self, eta: float = 0.0, generator=None, noisy_latents: Optional
     self.motion_scale = cfg.motion_guidance_weight
     from .. import lanes
     grp = lanes.group()
+    if grp is not None and grp.size > 1 and _context(cfg, noisy_latents.shape[2])[1]:
+        raise NotImplementedError("context_length: a launcher lane that packs several examples (--batch V > 1) with context "
+                                  "windows is not supported; run with --batch 1")
     packed = _group_sample(self, grp, noisy_latents, eta, generator) if grp is not None and grp.size > 1 else None
     if packed is not None:     # the thread's lane carried this example through one packed launch sequence with its fellows'
         noisy_latents = packed
@@ -538,6 +615,8 @@ def sample_video_batch(self, examples, eta: float = 0.0, decode=True):
         finally:
             for k, v in old.items():
                 setattr(cfg, k, v)
+    if getattr(cfg, "context_length", None) is not None and _context(cfg, cfg.video_length)[1]:
+        raise NotImplementedError("context_length: sample_video_batch with several examples and context windows is not supported")
     topks = [_motion_topk(cfg, ex.get("motion_topk")) for ex in examples]
     if len(set(topks)) != 1:
         raise ValueError("the motion representations of one packed batch differ in their top-k: %s" % topks)
