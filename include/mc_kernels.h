@@ -174,6 +174,25 @@ int mc_groupnorm_bwd_f16(const void* a, const void* b, int lda, int ldb, int c1,
                          int silu, float* partial, float* bstats, void* dx, int lddx, int accumulate,
                          void* stream);
 
+/* ---- video-wide GroupNorm(32) [+SiLU] ----------------------------------------------------------
+ * torch.nn.GroupNorm on [B, C, F, H, W] (resnet.py:143-165 with use_inflated_groupnorm = false; unet.py:244): the entries above
+ * with ONE statistic per (video, group) over `span` adjacent frames, span * hw * ctot / 32 elements.  frames % span != 0 or
+ * span < 1: MC_ERR_SHAPE, nothing launched.  stats: float[(frames / span) * 32 * 2]; partial as above (the per-(frame, chunk)
+ * sums are unchanged, a video's are one contiguous run); bstats: float[(frames / span) * 64] =
+ * mc_workspace_bytes_groupnorm_bwd_stats_span(frames, span).  span == 1 issues the per-frame entry's launches (same bits).
+ * span > 1: the statistics pass (not for the _partial_ entry), ONE finalize launch per norm (32 x frames / span workgroups, fixed
+ * summation order, no atomics), then the apply / backward pass.  Two sources, silu and accumulate as above. */
+long mc_workspace_bytes_groupnorm_bwd_stats_span(int frames, int span);
+int mc_groupnorm_fwd_span_f16(const void* a, const void* b, int lda, int ldb, int c1, int ctot, int frames, int hw, int span,
+                              float eps, float* partial, float* stats, const float* gamma, const float* beta, void* out, int ldo,
+                              int silu, void* stream);
+int mc_groupnorm_fwd_partial_span_f16(const void* a, int lda, int ctot, int frames, int hw, int span, float eps,
+                                      const float* partial, int pchunks, float* stats, const float* gamma, const float* beta,
+                                      void* out, int ldo, int silu, void* stream);
+int mc_groupnorm_bwd_span_f16(const void* a, const void* b, int lda, int ldb, int c1, int ctot, int frames, int hw, int span,
+                              const void* dz, int lddz, const float* stats, const float* gamma, const float* beta, int silu,
+                              float* partial, float* bstats, void* dx, int lddx, int accumulate, void* stream);
+
 /* ---- LayerNorm ------------------------------------------------------------------------------
  * attention.py:189,206,212; motion_module.py:204,210.  pe (optional, float[nframes_pe][C]) is the
  * sinusoidal temporal table of motion_module.py:237-246, added to row m at frame (m / hw) % nframes_pe

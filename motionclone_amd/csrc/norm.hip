@@ -268,6 +268,186 @@ __global__ void gn_bwd_apply_kernel(GnSrc s, const half_t* dz, int lddz, const f
     }
 }
 
+// ---- video-wide GroupNorm: statistics over `span` adjacent frames --------------------------------
+// torch.nn.GroupNorm on [B, C, F, H, W] (resnet.py:143-165 with use_inflated_groupnorm = false): one (mean, rstd) per
+// (video, group) over span * hw * cpg elements.  Rows are [(b f y x), C], so the per-(frame, chunk) partials of a video are
+// one contiguous run of span * pchunks entries: the statistics pass (gn_partial_kernel) and the conv epilogue's producer
+// are used as they are.  A video is finalised ONCE, by the launch below; the apply / backward passes then only look the
+// statistic of frame / span up (no serial walk over span * pchunks partials in every workgroup's prologue).
+
+// grid (32 groups, videos), block GN_SPAN_FIN threads: thread t adds items t, t + GN_SPAN_FIN, ... of the run in that order
+// (independent 8-byte loads), then a fixed binary tree in LDS: the same bits whatever grid the consumers run on.
+// mode 0: (sum, sumsq) -> (mean, rstd);  mode 1: (s1, s2) -> (s1 / n, s2 / n)
+constexpr int GN_SPAN_FIN = 256;
+
+__global__ __launch_bounds__(GN_SPAN_FIN) void gn_finalize_span_kernel(const float* partial, float* stats, int items, float n,
+                                                                        float eps, int mode) {
+    __shared__ float sa[GN_SPAN_FIN], sb[GN_SPAN_FIN];
+    const int t = threadIdx.x;
+    const int g = blockIdx.x, video = blockIdx.y;
+    const float* q = partial + ((size_t)video * items * 32 + g) * 2;
+    float a = 0.f, b = 0.f;
+    for (int it = t; it < items; it += GN_SPAN_FIN) {
+        a += q[(size_t)it * 64];
+        b += q[(size_t)it * 64 + 1];
+    }
+    sa[t] = a;
+    sb[t] = b;
+    __syncthreads();
+    for (int w = GN_SPAN_FIN / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            sa[t] += sa[t + w];
+            sb[t] += sb[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        a = sa[0];
+        b = sb[0];
+        float* o = stats + ((size_t)video * 32 + g) * 2;
+        if (mode == 0) {
+            const float mean = a / n;
+            const float var = fmaxf(b / n - mean * mean, 0.f);
+            o[0] = mean;
+            o[1] = 1.0f / sqrtf(var + eps);
+        } else {
+            o[0] = a / n;
+            o[1] = b / n;
+        }
+    }
+}
+
+// gn_apply_kernel with the statistics of frame / span (always read from `stats`, which gn_finalize_span_kernel wrote)
+__global__ void gn_apply_span_kernel(GnSrc s, const float* stats, const float* gamma, const float* beta, half_t* out, int ldo,
+                                     int R, int nchunk, int silu, int span) {
+    const int VC = s.ctot / 8;
+    const int t = threadIdx.x;
+    const int col = t % VC, r = t / VC;
+    const int frame = blockIdx.y, chunk = blockIdx.x;
+    if (r >= R) return;
+    const int per = (s.hw + nchunk - 1) / nchunk;
+    const int t0 = chunk * per;
+    const int t1 = min(s.hw, t0 + per);
+    const float* vst = stats + (size_t)(frame / span) * 64;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        int c = col * 8 + e;
+        const float* st = vst + (c / s.cpg) * 2;
+        sc[e] = st[1] * gamma[c];
+        sh[e] = beta[c] - st[0] * sc[e];
+    }
+    for (int tk = t0 + r; tk < t1; tk += R) {
+        size_t tok = (size_t)frame * s.hw + tk;
+        half8_t v = gn_load(s, tok, col * 8);
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float y = (float)v[e] * sc[e] + sh[e];
+            if (silu) y = silu_f(y);
+            o[e] = to_half(y);
+        }
+        st8(out + tok * ldo + col * 8, o);
+    }
+}
+
+// gn_bwd_partial_kernel with the statistics of frame / span: per (frame, chunk, group) sums of dxhat and dxhat * xhat
+__global__ void gn_bwd_partial_span_kernel(GnSrc s, const half_t* dz, int lddz, const float* stats, const float* gamma,
+                                           const float* beta, int silu, int R, int nchunk, int span, float* partial) {
+    MC_DYN_SMEM(smem);
+    float* s1 = reinterpret_cast<float*>(smem);
+    float* s2 = s1 + R * s.ctot;
+    const int VC = s.ctot / 8;
+    const int t = threadIdx.x;
+    const int col = t % VC, r = t / VC;
+    const int frame = blockIdx.y, chunk = blockIdx.x;
+    const int per = (s.hw + nchunk - 1) / nchunk;
+    const int t0 = chunk * per;
+    const int t1 = min(s.hw, t0 + per);
+    float a[8], b[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = b[e] = 0.f;
+    if (r < R) {
+        const float* vst = stats + (size_t)(frame / span) * 64;
+        float mean[8], rstd[8], gm[8], bt[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            int c = col * 8 + e;
+            mean[e] = vst[(c / s.cpg) * 2];
+            rstd[e] = vst[(c / s.cpg) * 2 + 1];
+            gm[e] = gamma[c];
+            bt[e] = beta[c];
+        }
+        for (int tk = t0 + r; tk < t1; tk += R) {
+            size_t tok = (size_t)frame * s.hw + tk;
+            half8_t x = gn_load(s, tok, col * 8);
+            half8_t g = ld8(dz + tok * lddz + col * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float xh = ((float)x[e] - mean[e]) * rstd[e];
+                float dy = (float)g[e];
+                if (silu) dy *= silu_grad_f(xh * gm[e] + bt[e]);
+                float dxh = dy * gm[e];
+                a[e] += dxh;
+                b[e] += dxh * xh;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            s1[r * s.ctot + col * 8 + e] = a[e];
+            s2[r * s.ctot + col * 8 + e] = b[e];
+        }
+    }
+    __syncthreads();
+    gn_group_totals(s1, s2, R, s.ctot, s.cpg, partial + (size_t)(frame * nchunk + chunk) * 64);
+}
+
+// gn_bwd_apply_kernel with both means over the video's group elements (`bstats`, finalised by gn_finalize_span_kernel mode 1)
+__global__ void gn_bwd_apply_span_kernel(GnSrc s, const half_t* dz, int lddz, const float* stats, const float* bstats,
+                                         const float* gamma, const float* beta, int silu, half_t* dx, int lddx, int R,
+                                         int nchunk, int accumulate, int span) {
+    const int VC = s.ctot / 8;
+    const int t = threadIdx.x;
+    const int col = t % VC, r = t / VC;
+    const int frame = blockIdx.y, chunk = blockIdx.x;
+    if (r >= R) return;
+    const int per = (s.hw + nchunk - 1) / nchunk;
+    const int t0 = chunk * per;
+    const int t1 = min(s.hw, t0 + per);
+    const float* vst = stats + (size_t)(frame / span) * 64;
+    const float* vbs = bstats + (size_t)(frame / span) * 64;
+    float mean[8], rstd[8], gm[8], bt[8], m1[8], m2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        int c = col * 8 + e;
+        const int gi = (c / s.cpg) * 2;
+        mean[e] = vst[gi];
+        rstd[e] = vst[gi + 1];
+        m1[e] = vbs[gi];
+        m2[e] = vbs[gi + 1];
+        gm[e] = gamma[c];
+        bt[e] = beta[c];
+    }
+    for (int tk = t0 + r; tk < t1; tk += R) {
+        size_t tok = (size_t)frame * s.hw + tk;
+        half8_t x = gn_load(s, tok, col * 8);
+        half8_t g = ld8(dz + tok * lddz + col * 8);
+        half8_t prev;
+        if (accumulate) prev = ld8(dx + tok * lddx + col * 8);
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float xh = ((float)x[e] - mean[e]) * rstd[e];
+            float dy = (float)g[e];
+            if (silu) dy *= silu_grad_f(xh * gm[e] + bt[e]);
+            float v = rstd[e] * (dy * gm[e] - m1[e] - xh * m2[e]);
+            if (accumulate) v += (float)prev[e];
+            o[e] = to_half(v);
+        }
+        st8(dx + tok * lddx + col * 8, o);
+    }
+}
+
 // ---- LayerNorm: one wave per row, row kept in registers ----------------------------------
 // A wave walks LN_RPW consecutive rows (fully unrolled, so the loads of all of them are in flight together).
 // gamma / beta of the lane's 8-channel vectors are loaded once per wave as 16-byte vectors.
@@ -638,6 +818,79 @@ extern "C" int mc_groupnorm_bwd_f16(const void* a, const void* b, int lda, int l
     MC_LAUNCH(gn_bwd_apply_kernel, dim3(nchunk, frames), dim3(threads), 0, (hipStream_t)stream, s, (const half_t*)dz,
               lddz, stats, bstats, gamma, beta, silu, (half_t*)dx, lddx, R, nchunk, accumulate, (const float*)partial,
               (float)hw * s.cpg);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// ---- video-wide GroupNorm entries: statistics per (frames / span videos, group) ---------------------------------------------
+// span == 1 IS the per-frame entry (the same launches, the same bits).  span > 1: statistics pass (or the producer's partials),
+// one finalize launch per norm, apply / backward passes that look the video's statistic up.
+extern "C" long mc_workspace_bytes_groupnorm_bwd_stats_span(int frames, int span) {
+    return (frames <= 0 || span < 1 || frames % span) ? -1 : (long)sizeof(float) * (frames / span) * 64;
+}
+
+static int span_ok(int frames, int span) { return frames > 0 && span >= 1 && frames % span == 0; }
+
+extern "C" int mc_groupnorm_fwd_span_f16(const void* a, const void* b, int lda, int ldb, int c1, int ctot, int frames, int hw,
+                                         int span, float eps, float* partial, float* stats, const float* gamma,
+                                         const float* beta, void* out, int ldo, int silu, void* stream) {
+    if (!span_ok(frames, span)) return MC_ERR_SHAPE;
+    if (span == 1)
+        return mc_groupnorm_fwd_f16(a, b, lda, ldb, c1, ctot, frames, hw, eps, partial, stats, gamma, beta, out, ldo, silu, stream);
+    GnSrc s;
+    if (!make_src(&s, a, b, lda, ldb, c1, ctot, hw) || hw <= 0 || ldo % 8) return MC_ERR_SHAPE;
+    int R, threads;
+    if (!gn_geometry(ctot, &R, &threads) || threads < 64) return MC_ERR_UNSUPPORTED;
+    const int nchunk = mc_gn_nchunk(hw);
+    const size_t smem = (size_t)2 * R * ctot * sizeof(float);
+    MC_LAUNCH(gn_partial_kernel, dim3(nchunk, frames), dim3(threads), smem, (hipStream_t)stream, s, R, nchunk, partial);
+    MC_LAUNCH(gn_finalize_span_kernel, dim3(32, frames / span), dim3(GN_SPAN_FIN), 0, (hipStream_t)stream, (const float*)partial,
+              stats, span * nchunk, (float)span * hw * s.cpg, eps, 0);
+    MC_LAUNCH(gn_apply_span_kernel, dim3(nchunk, frames), dim3(threads), 0, (hipStream_t)stream, s, (const float*)stats, gamma,
+              beta, (half_t*)out, ldo, R, nchunk, silu, span);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+extern "C" int mc_groupnorm_fwd_partial_span_f16(const void* a, int lda, int ctot, int frames, int hw, int span, float eps,
+                                                 const float* partial, int pchunks, float* stats, const float* gamma,
+                                                 const float* beta, void* out, int ldo, int silu, void* stream) {
+    if (!span_ok(frames, span)) return MC_ERR_SHAPE;
+    if (span == 1)
+        return mc_groupnorm_fwd_partial_f16(a, lda, ctot, frames, hw, eps, partial, pchunks, stats, gamma, beta, out, ldo, silu,
+                                            stream);
+    GnSrc s;
+    if (!make_src(&s, a, nullptr, lda, 0, ctot, ctot, hw) || hw <= 0 || ldo % 8) return MC_ERR_SHAPE;
+    if (!partial || pchunks <= 0 || pchunks > 256) return MC_ERR_SHAPE;
+    int R, threads;
+    if (!gn_geometry(ctot, &R, &threads) || threads < 64) return MC_ERR_UNSUPPORTED;
+    const int nchunk = mc_gn_nchunk(hw);
+    MC_LAUNCH(gn_finalize_span_kernel, dim3(32, frames / span), dim3(GN_SPAN_FIN), 0, (hipStream_t)stream, partial, stats,
+              span * pchunks, (float)span * hw * s.cpg, eps, 0);
+    MC_LAUNCH(gn_apply_span_kernel, dim3(nchunk, frames), dim3(threads), 0, (hipStream_t)stream, s, (const float*)stats, gamma,
+              beta, (half_t*)out, ldo, R, nchunk, silu, span);
+    return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
+}
+
+// workspace: partial as for mc_groupnorm_bwd_f16 + bstats float[(frames / span) * 64]
+extern "C" int mc_groupnorm_bwd_span_f16(const void* a, const void* b, int lda, int ldb, int c1, int ctot, int frames, int hw,
+                                         int span, const void* dz, int lddz, const float* stats, const float* gamma,
+                                         const float* beta, int silu, float* partial, float* bstats, void* dx, int lddx,
+                                         int accumulate, void* stream) {
+    if (!span_ok(frames, span)) return MC_ERR_SHAPE;
+    if (span == 1)
+        return mc_groupnorm_bwd_f16(a, b, lda, ldb, c1, ctot, frames, hw, dz, lddz, stats, gamma, beta, silu, partial, bstats, dx,
+                                    lddx, accumulate, stream);
+    GnSrc s;
+    if (!make_src(&s, a, b, lda, ldb, c1, ctot, hw) || hw <= 0 || lddz % 8 || lddx % 8) return MC_ERR_SHAPE;
+    int R, threads;
+    if (!gn_geometry(ctot, &R, &threads) || threads < 64) return MC_ERR_UNSUPPORTED;
+    const int nchunk = mc_gn_nchunk(hw);
+    const size_t smem = (size_t)2 * R * ctot * sizeof(float);
+    MC_LAUNCH(gn_bwd_partial_span_kernel, dim3(nchunk, frames), dim3(threads), smem, (hipStream_t)stream, s, (const half_t*)dz,
+              lddz, stats, gamma, beta, silu, R, nchunk, span, partial);
+    MC_LAUNCH(gn_finalize_span_kernel, dim3(32, frames / span), dim3(GN_SPAN_FIN), 0, (hipStream_t)stream, (const float*)partial,
+              bstats, span * nchunk, (float)span * hw * s.cpg, 0.f, 1);
+    MC_LAUNCH(gn_bwd_apply_span_kernel, dim3(nchunk, frames), dim3(threads), 0, (hipStream_t)stream, s, (const half_t*)dz, lddz,
+              stats, (const float*)bstats, gamma, beta, silu, (half_t*)dx, lddx, R, nchunk, accumulate, span);
     return MC_LAST_ERROR() ? MC_ERR_LAUNCH : MC_OK;
 }
 

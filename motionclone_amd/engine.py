@@ -76,11 +76,31 @@ def reduce_motion_mask(mask64, grid, hw):
 
 
 def default_config():
-    """SD-1.5 UNet + configs/model_config/model_config.yaml (the only architecture the reference ships)."""
+    """SD-1.5 UNet + configs/model_config/model_config.yaml (the AnimateDiff v3 layout).  The layout keys (LAYOUT_DEFAULTS;
+    a config dict may leave them out) select the v1 / v2 layouts of inference-v1.yaml / inference-v2.yaml."""
     return dict(in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
                 cross_attention_dim=768, attention_heads=8, norm_num_groups=32, norm_eps=1e-5,
                 down_has_attn=(True, True, True, False), up_has_attn=(False, True, True, True),
-                motion_heads=8, motion_pe_max_len=32, motion_mid_block=False)
+                motion_heads=8, motion_pe_max_len=32, **LAYOUT_DEFAULTS)
+
+
+# inflated_groupnorm: GroupNorm of the ResnetBlock3Ds and conv_norm_out per frame (True: InflatedGroupNorm, v2 / v3) or per
+#   video (False: torch.nn.GroupNorm on [B, C, F, H, W], v1; reference resnet.py:143-165, unet.py:244)
+# motion_mid_block: a motion module between the mid block's attention and its second resnet (v2; unet_blocks.py:271-278)
+# motion_decoder_only: no motion modules in the down blocks;  motion_resolutions: a motion module at level i (down block i,
+#   up block 3 - i) only when 2 ** i is listed (unet.py:157,236)
+LAYOUT_DEFAULTS = dict(inflated_groupnorm=True, motion_mid_block=False, motion_decoder_only=False, motion_resolutions=(1, 2, 4, 8))
+MID_MOTION = "mid_block.motion_modules.0"
+
+
+def has_motion(cfg, where, i):
+    """does the layout `cfg` carry motion modules in down block i / up block i / the mid block (`where` = 'down', 'up', 'mid')?"""
+    if where == "mid":
+        return bool(cfg.get("motion_mid_block", False))
+    if where == "down" and cfg.get("motion_decoder_only", False):
+        return False
+    level = i if where == "down" else 3 - i
+    return (2 ** level) in tuple(cfg.get("motion_resolutions", (1, 2, 4, 8)))
 
 
 class Geo:
@@ -255,7 +275,16 @@ class UNet3DEngine:
         if guidance_blocks is None:
             guidance_blocks = ["up_blocks.%d" % guidance_block]
         self.guidance_blocks = tuple(guidance_blocks)
-        self.guidance_block = int(self.guidance_blocks[-1].split(".")[-1])
+        for k, v in LAYOUT_DEFAULTS.items():
+            self.cfg.setdefault(k, v)
+        self.cfg["motion_resolutions"] = tuple(int(r) for r in self.cfg["motion_resolutions"])
+        try:
+            self.guidance_block = int(self.guidance_blocks[-1].split(".")[-1])
+        except ValueError:
+            # the reference evaluates int(motion_guidance_blocks[-1].split(".")[-1]) (motionclone_functions.py:602)
+            raise ValueError("motion_guidance_blocks %r: the last entry must name an up block ('up_blocks.N' - it bounds the "
+                             "differentiated half); %r cannot be last, put it in front of an 'up_blocks.N' entry"
+                             % (list(self.guidance_blocks), self.guidance_blocks[-1])) from None
         for blk in self.guidance_blocks:
             kind, _, idx = blk.partition(".")
             if kind not in ("down_blocks", "up_blocks", "mid_block") or (kind == "up_blocks" and idx.split(".")[0].isdigit()
@@ -275,6 +304,19 @@ class UNet3DEngine:
         ch = self.cfg["block_out_channels"]
         assert all(c % 64 == 0 for c in ch) and self.cfg["cross_attention_dim"] % 64 == 0
         self._build_temb_plan()
+        self._check_hooks()
+
+    def _check_hooks(self):
+        if not self.hooked_names():
+            raise ValueError("motion_guidance_blocks %r hook no temporal attention of this layout (motion modules: down blocks %s, "
+                             "mid block %s, up blocks %s; up blocks behind up_blocks.%d are outside the guidance graph)"
+                             % (list(self.guidance_blocks), [i for i in range(4) if has_motion(self.cfg, "down", i)],
+                                has_motion(self.cfg, "mid", 0), [i for i in range(4) if has_motion(self.cfg, "up", i)],
+                                self.guidance_block))
+
+    def _span(self, geo):
+        """frames per GroupNorm statistic of the ResnetBlock3Ds and conv_norm_out: 1 (per frame) or the video's F"""
+        return 1 if self.cfg["inflated_groupnorm"] else geo.F
 
     # ---- time embedding: all time_emb_proj Linears as one GEMM ----------------------------------
     def _resnet_names(self):
@@ -418,6 +460,7 @@ class UNet3DEngine:
         w, cfg = self.w, self.cfg
         eps = cfg["norm_eps"]
         fr, hw, H, W = geo.frames, geo.hw, geo.H, geo.W
+        span = self._span(geo)       # > 1: video-wide statistics (the per-frame partials of conv1 / conv2 still serve them)
         off, cout = self.temb_off[p]
         tb = tb_all[:, off:off + cout]        # one shared row [1, cout] (a contiguous view), or one row per batch element
         rpb = 0
@@ -425,12 +468,12 @@ class UNet3DEngine:
             tb, rpb = tb.contiguous(), geo.F * hw
         g1w, b1 = w.vec(p + "norm1.weight"), w.vec(p + "norm1.bias")
         g2, b2 = w.vec(p + "norm2.weight"), w.vec(p + "norm2.bias")
-        h1, st1 = ops.gn_fwd(x, x2, g1w, b1, True, fr, hw, eps, gnp=ops.gnp_of(x, hw) if x2 is None else None)
+        h1, st1 = ops.gn_fwd(x, x2, g1w, b1, True, fr, hw, eps, gnp=ops.gnp_of(x, hw) if x2 is None else None, span=span)
         # (round 6) norm2's statistics come from conv1's epilogue where the library runs a one-pass ring kernel (gp; else None)
         h2, gp = ops.gemm(h1, w.conv(p + "conv1.weight"), bias=tb, rows_per_batch=rpb, mode=CONV_S1,
                           geom=(H, W, H, W), m_out=geo.T, gn_hw=hw)
         del h1
-        h3, st2 = ops.gn_fwd(h2, None, g2, b2, True, fr, hw, eps, gnp=gp)
+        h3, st2 = ops.gn_fwd(h2, None, g2, b2, True, fr, hw, eps, gnp=gp, span=span)
         has_sc = (p + "conv_shortcut.weight") in w.sd
         if has_sc:
             sc = ops.gemm(x, w.lin(p + "conv_shortcut.weight"), a2=x2,
@@ -453,13 +496,13 @@ class UNet3DEngine:
                 if dout is None:
                     return
                 dh3 = ops.gemm(dout, w.conv_dgrad(p + "conv2.weight"), mode=CONV_S1, geom=(H1, W1, H1, W1), m_out=g1.T)
-                dh2 = ops.gn_bwd(bh2, None, dh3, bst2, g2, b2, True, fr1, hw1)
+                dh2 = ops.gn_bwd(bh2, None, dh3, bst2, g2, b2, True, fr1, hw1, span=span)
                 dh1 = ops.gemm(dh2, w.conv_dgrad(p + "conv1.weight"), mode=CONV_S1, geom=(H1, W1, H1, W1), m_out=g1.T)
                 if has_sc:
-                    dx = ops.gn_bwd(bx, bx2, dh1, bst1, g1w, b1, True, fr1, hw1)
+                    dx = ops.gn_bwd(bx, bx2, dh1, bst1, g1w, b1, True, fr1, hw1, span=span)
                     ops.gemm(dout, w.lin_t(p + "conv_shortcut.weight"), residual=dx, out=dx)
                 else:
-                    dx = ops.gn_bwd(bx, None, dh1, bst1, g1w, b1, True, fr1, hw1, out=dout, accumulate=True)
+                    dx = ops.gn_bwd(bx, None, dh1, bst1, g1w, b1, True, fr1, hw1, out=dout, accumulate=True, span=span)
                 c1 = x.shape[1]
                 if x2 is None:
                     tape.give(x, dx)
@@ -562,6 +605,9 @@ class UNet3DEngine:
         p = name + ".temporal_transformer."
         b = p + "transformer_blocks.0."
         gN, bN = w.vec(p + "norm.weight"), w.vec(p + "norm.bias")
+        if geo.F > cfg["motion_pe_max_len"]:
+            raise ValueError("a run of %d frames exceeds the motion modules' position table of %d entries "
+                             "(temporal_position_encoding_max_len)" % (geo.F, cfg["motion_pe_max_len"]))
         pe = w.pe(C)[:geo.F].contiguous()
         h, st = self._gn_gemm(x, p + "norm.weight", p + "norm.bias", p + "proj_in.weight", p + "proj_in.bias", fr, hw)
         saved = []
@@ -736,7 +782,8 @@ class UNet3DEngine:
                     if cfg["down_has_attn"][i]:
                         x = self._spatial("down_blocks.%d.attentions.%d." % (i, j), x, text2d, n_text, geo, tape)
                 nm = "down_blocks.%d.motion_modules.%d" % (i, j)
-                x = self._motion(nm, x, geo, tape, record if hook(nm) else None, seeds if hook(nm) else None)
+                if has_motion(cfg, "down", i):
+                    x = self._motion(nm, x, geo, tape, record if hook(nm) else None, seeds if hook(nm) else None)
                 skips.append((x, geo))
             if i < 3:
                 x, geo = self._downsample("down_blocks.%d.downsamplers.0.conv." % i, x, geo, tape)
@@ -753,6 +800,8 @@ class UNet3DEngine:
                     tape.add(lambda sk=sk, summed=summed: (lambda g: tape.give(sk, g) if g is not None else None)(tape.take(summed)))
         x = self._resnet("mid_block.resnets.0.", x, None, tb_all, geo, tape)
         x = self._spatial("mid_block.attentions.0.", x, text2d, n_text, geo, tape)
+        if has_motion(cfg, "mid", 0):    # resnet 0, attention, motion module, resnet 1 (unet_blocks.py:271-278)
+            x = self._motion(MID_MOTION, x, geo, tape, record if hook(MID_MOTION) else None, seeds if hook(MID_MOTION) else None)
         x = self._resnet("mid_block.resnets.1.", x, None, tb_all, geo, tape)
         if mid_residual is not None:   # :595-598
             xm = x
@@ -772,11 +821,13 @@ class UNet3DEngine:
                     x = self._spatial("up_blocks.%d.attentions.%d." % (i, j), x, text2d, n_text, geo, tp)
                 nm = "up_blocks.%d.motion_modules.%d" % (i, j)
                 is_hooked = in_graph and hook(nm)
-                x = self._motion(nm, x, geo, tp, record if is_hooked else None, seeds if is_hooked else None)
+                if has_motion(cfg, "up", i):
+                    x = self._motion(nm, x, geo, tp, record if is_hooked else None, seeds if is_hooked else None)
             if i < 3:
                 # the upsampler of block i feeds block i+1: in the graph only while i+1 <= guidance block
                 x, geo = self._upsample("up_blocks.%d.upsamplers.0.conv." % i, x, geo, tape if i < gb else None)
-        hn, st = ops.gn_fwd(x, None, w.vec("conv_norm_out.weight"), w.vec("conv_norm_out.bias"), True, geo.frames, geo.hw, cfg["norm_eps"])
+        hn, st = ops.gn_fwd(x, None, w.vec("conv_norm_out.weight"), w.vec("conv_norm_out.bias"), True, geo.frames, geo.hw, cfg["norm_eps"],
+                            span=self._span(geo))
         eps = ops.gemm(hn, w.conv("conv_out.weight"), bias=w.vec("conv_out.bias").unsqueeze(0), mode=CONV_S1,
                        geom=(geo.H, geo.W, geo.H, geo.W), m_out=geo.T)
         return eps
@@ -786,10 +837,14 @@ class UNet3DEngine:
         return any(blk in attention_name for blk in self.guidance_blocks)
 
     def hooked_names(self):
-        """names of the hooked temporal attentions in module order (= the keys of the reference's .pt dict)"""
-        L = self.cfg["layers_per_block"]
-        mods = ["down_blocks.%d.motion_modules.%d" % (i, j) for i in range(4) for j in range(L)]
-        mods += ["up_blocks.%d.motion_modules.%d" % (i, j) for i in range(self.guidance_block + 1) for j in range(L + 1)]
+        """names of the hooked temporal attentions in module order (= the keys of the reference's .pt dict): the reference's
+        named_modules() yields the down blocks, the up blocks, then the mid block"""
+        L, cfg = self.cfg["layers_per_block"], self.cfg
+        mods = ["down_blocks.%d.motion_modules.%d" % (i, j) for i in range(4) if has_motion(cfg, "down", i) for j in range(L)]
+        mods += ["up_blocks.%d.motion_modules.%d" % (i, j) for i in range(self.guidance_block + 1) if has_motion(cfg, "up", i)
+                 for j in range(L + 1)]
+        if has_motion(cfg, "mid", 0):
+            mods.append(MID_MOTION)
         names = [m + ".temporal_transformer.transformer_blocks.0.attention_blocks.%d" % a for m in mods for a in range(2)]
         return [n for n in names if any(blk in n for blk in self.guidance_blocks)]
 
@@ -1096,6 +1151,12 @@ class ControlNetEngine(UNet3DEngine):
         for i in range(4):
             names += ["down_blocks.%d.resnets.%d." % (i, j) for j in range(L)]
         return names + ["mid_block.resnets.0.", "mid_block.resnets.1."]
+
+    def _check_hooks(self):
+        pass     # inference-only: nothing is hooked
+
+    def _span(self, geo):
+        return 1     # the encoder's GroupNorms are per frame whatever the UNet's layout (sparse_controlnet.py:272,310)
 
     def _cond_embedding(self, cond, mask, F, H, W):
         """controlnet_cond_embedding(cat(cond, mask)) + conv_in.bias (:516-527) as a token matrix [(v f y x), C0] for the

@@ -49,6 +49,10 @@ SIGNATURES = {
     "mc_groupnorm_fwd_f16": [P, P, I, I, I, I, I, I, F, P, P, P, P, P, I, I, P],
     "mc_groupnorm_fwd_partial_f16": [P, I, I, I, I, F, P, I, P, P, P, P, I, I, P],
     "mc_groupnorm_bwd_f16": [P, P, I, I, I, I, I, I, P, I, P, P, P, I, P, P, P, I, I, P],
+    "mc_workspace_bytes_groupnorm_bwd_stats_span": [I, I],
+    "mc_groupnorm_fwd_span_f16": [P, P, I, I, I, I, I, I, I, F, P, P, P, P, P, I, I, P],
+    "mc_groupnorm_fwd_partial_span_f16": [P, I, I, I, I, I, F, P, I, P, P, P, P, I, I, P],
+    "mc_groupnorm_bwd_span_f16": [P, P, I, I, I, I, I, I, I, P, I, P, P, P, I, P, P, P, I, I, P],
     "mc_layernorm_fwd_f16": [P, I, P, I, P, P, P, I, I, P, I, I, F, P],
     "mc_layernorm_bwd_f16": [P, I, P, I, P, P, P, I, P, I, I, I, P],
     "mc_attn_fwd_f16": [P, P, P, I, I, I, P, I, P, I, I, I, I, I, I, F, P],

@@ -90,26 +90,52 @@ class UNet3DConditionModel(nn.Module):
     def __init__(self, sample_size=None, in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280),
                  layers_per_block=2, cross_attention_dim=768, attention_head_dim=8, norm_num_groups=32, norm_eps=1e-5,
                  use_motion_module=True, motion_module_resolutions=(1, 2, 4, 8), motion_module_mid_block=False,
-                 motion_module_type="Vanilla", motion_module_kwargs=None, use_inflated_groupnorm=True, **unused):
+                 motion_module_type="Vanilla", motion_module_kwargs=None, use_inflated_groupnorm=True,
+                 motion_module_decoder_only=False, unet_use_cross_frame_attention=False, unet_use_temporal_attention=False,
+                 **unused):
+        """The layouts of configs/model_config/model_config.yaml (AnimateDiff v3), inference-v2.yaml (motion_module_mid_block)
+        and inference-v1.yaml (use_inflated_groupnorm = false, 24 positions), and every combination of those switches with
+        motion_module_decoder_only / motion_module_resolutions.  What is not built raises NotImplementedError by name."""
         super().__init__()
         mk = dict(motion_module_kwargs or {})
-        if not use_motion_module or motion_module_mid_block or tuple(motion_module_resolutions) != (1, 2, 4, 8):
-            raise NotImplementedError("only the AnimateDiff layout of configs/model_config/model_config.yaml is built")
-        if mk.get("attention_block_types", ["Temporal_Self", "Temporal_Self"]) != ["Temporal_Self", "Temporal_Self"] \
-                or mk.get("num_transformer_block", 1) != 1 or not mk.get("temporal_position_encoding", True):
-            raise NotImplementedError("motion_module_kwargs other than the v3_sd15_mm layout")
+        if not use_motion_module:
+            raise NotImplementedError("use_motion_module = false: a UNet without motion modules is not built")
+        if motion_module_type != "Vanilla":
+            raise NotImplementedError("motion_module_type %r: only 'Vanilla' is built" % (motion_module_type,))
+        if unet_use_cross_frame_attention or unet_use_temporal_attention:
+            raise NotImplementedError("unet_use_cross_frame_attention / unet_use_temporal_attention are not built")
+        types = list(mk.get("attention_block_types", ["Temporal_Self", "Temporal_Self"]))
+        if types != ["Temporal_Self", "Temporal_Self"]:
+            raise NotImplementedError("motion_module_kwargs.attention_block_types %r: only two Temporal_Self blocks are built" % (types,))
+        if mk.get("num_transformer_block", 1) != 1:
+            raise NotImplementedError("motion_module_kwargs.num_transformer_block = %r: only 1 is built" % (mk["num_transformer_block"],))
+        if not mk.get("temporal_position_encoding", True):
+            raise NotImplementedError("motion_module_kwargs.temporal_position_encoding = false is not built")
+        if mk.get("temporal_attention_dim_div", 1) != 1:
+            raise NotImplementedError("motion_module_kwargs.temporal_attention_dim_div = %r: only 1 is built"
+                                      % (mk["temporal_attention_dim_div"],))
+        resolutions = tuple(int(r) for r in motion_module_resolutions)
         heads = attention_head_dim if isinstance(attention_head_dim, int) else attention_head_dim[0]
         self.engine_config = dict(default_config(), in_channels=in_channels, out_channels=out_channels,
                                   block_out_channels=tuple(block_out_channels), layers_per_block=layers_per_block,
                                   cross_attention_dim=cross_attention_dim, attention_heads=heads,
                                   norm_num_groups=norm_num_groups, norm_eps=norm_eps,
                                   motion_heads=mk.get("num_attention_heads", 8),
-                                  motion_pe_max_len=mk.get("temporal_position_encoding_max_len", 32))
+                                  motion_pe_max_len=mk.get("temporal_position_encoding_max_len", 32),
+                                  inflated_groupnorm=bool(use_inflated_groupnorm), motion_mid_block=bool(motion_module_mid_block),
+                                  motion_decoder_only=bool(motion_module_decoder_only), motion_resolutions=resolutions)
         self.config = FrozenConfig(sample_size=sample_size, in_channels=in_channels, out_channels=out_channels,
                                    block_out_channels=tuple(block_out_channels), layers_per_block=layers_per_block,
                                    cross_attention_dim=cross_attention_dim, attention_head_dim=attention_head_dim,
                                    norm_num_groups=norm_num_groups, norm_eps=norm_eps, center_input_sample=False)
-        _build_tree(self, spec.param_shapes(self.engine_config), self.engine_config, torch.float16)
+        shapes = spec.param_shapes(self.engine_config)
+        if self.engine_config["motion_mid_block"]:
+            # the reference registers the mid block behind the up blocks: named_modules() - and with it the key order of a
+            # motion representation - puts the mid-block temporal attentions last
+            order = sorted(shapes, key=lambda k: 2 if k.startswith("mid_block.") else 3 if k.startswith("conv_norm_out.")
+                           or k.startswith("conv_out.") else 1 if k.startswith("up_blocks.") else 0)
+            shapes = {k: shapes[k] for k in order}
+        _build_tree(self, shapes, self.engine_config, torch.float16)
         self.num_upsamplers = 3
         self.input_config = None
         self._engine = None

@@ -326,12 +326,16 @@ def gn_apply(x, x2, stats, gamma, beta, silu, frames, hw, out=None):
     return out
 
 
-def gn_fwd(x, x2, gamma, beta, silu, frames, hw, eps, out=None, gnp=None):
+def gn_fwd(x, x2, gamma, beta, silu, frames, hw, eps, out=None, gnp=None, span=1):
     """GroupNorm(32) (+ SiLU) of [frames * hw, c1 (+ c2)] tokens -> (out, stats); stats = (mean, rstd) per (frame, group) for
     the backward.  gn_stats + gn_apply without the finalize launch (mc_groupnorm_fwd_f16).
-    gnp = (partial, chunks per frame) from `gemm(..., gn_hw=hw)` that produced x: ONE launch, no statistics pass."""
+    gnp = (partial, chunks per frame) from `gemm(..., gn_hw=hw)` that produced x: ONE launch, no statistics pass.
+    span > 1: video-wide statistics (torch.nn.GroupNorm on [B, C, F, H, W]) - one (mean, rstd) per (frames / span videos,
+    group) over `span` adjacent frames (mc_groupnorm_fwd_span_f16 / _partial_span_): stats is [frames / span, 32, 2]."""
     c1 = x.shape[1]
     ctot = c1 + (x2.shape[1] if x2 is not None else 0)
+    if span != 1:
+        return _gn_fwd_span(x, x2, gamma, beta, silu, frames, hw, eps, out, gnp, int(span), c1, ctot)
     stats = empty((frames, 32, 2), x, torch.float32)
     if out is None:
         out = empty((frames * hw, ctot), x)
@@ -345,14 +349,41 @@ def gn_fwd(x, x2, gamma, beta, silu, frames, hw, eps, out=None, gnp=None):
     return out, stats
 
 
-def gn_bwd(x, x2, dz, stats, gamma, beta, silu, frames, hw, out=None, accumulate=False):
+def _gn_fwd_span(x, x2, gamma, beta, silu, frames, hw, eps, out, gnp, span, c1, ctot):
+    if span < 1 or frames % span:
+        raise ValueError("gn_fwd: %d frames are no whole number of videos of span = %d frames" % (frames, span))
+    stats = empty((frames // span, 32, 2), x, torch.float32)
+    if out is None:
+        out = empty((frames * hw, ctot), x)
+    if gnp is not None and x2 is None:
+        lib.call("mc_groupnorm_fwd_partial_span_f16", _p(x), _ld(x), ctot, frames, hw, span, float(eps), _p(gnp[0]), gnp[1],
+                 _p(stats), _p(_f32(gamma)), _p(_f32(beta)), _p(out), _ld(out), int(silu), _stream(x))
+        return out, stats
+    partial = workspace("groupnorm", x, frames, hw)
+    lib.call("mc_groupnorm_fwd_span_f16", _p(x), _p(x2), _ld(x), _ld(x2), c1, ctot, frames, hw, span, float(eps), _p(partial),
+             _p(stats), _p(_f32(gamma)), _p(_f32(beta)), _p(out), _ld(out), int(silu), _stream(x))
+    return out, stats
+
+
+def gn_bwd(x, x2, dz, stats, gamma, beta, silu, frames, hw, out=None, accumulate=False, span=1):
+    """span > 1: the backward of the video-wide form (stats [frames / span, 32, 2] from gn_fwd(..., span=span)); both means of
+    dx = rstd (g - mean(g) - xhat mean(g xhat)) run over the span * hw * C / 32 elements of the (video, group)"""
     c1 = x.shape[1]
     ctot = c1 + (x2.shape[1] if x2 is not None else 0)
     partial = workspace("groupnorm", x, frames, hw)
-    bstats = workspace("groupnorm_bwd_stats", x, frames)
     if out is None:
         assert not accumulate
         out = empty((frames * hw, ctot), x)
+    if span != 1:
+        span = int(span)
+        if span < 1 or frames % span:
+            raise ValueError("gn_bwd: %d frames are no whole number of videos of span = %d frames" % (frames, span))
+        bstats = workspace("groupnorm_bwd_stats_span", x, frames, span)
+        lib.call("mc_groupnorm_bwd_span_f16", _p(x), _p(x2), _ld(x), _ld(x2), c1, ctot, frames, hw, span, _p(dz), _ld(dz),
+                 _p(stats), _p(_f32(gamma)), _p(_f32(beta)), int(silu), _p(partial), _p(bstats), _p(out), _ld(out),
+                 int(accumulate), _stream(x))
+        return out
+    bstats = workspace("groupnorm_bwd_stats", x, frames)
     lib.call("mc_groupnorm_bwd_f16", _p(x), _p(x2), _ld(x), _ld(x2), c1, ctot, frames, hw, _p(dz), _ld(dz),
              _p(stats), _p(_f32(gamma)), _p(_f32(beta)), int(silu), _p(partial), _p(bstats), _p(out), _ld(out),
              int(accumulate), _stream(x))

@@ -75,7 +75,18 @@ def _motion(s, p, c):
     s[p + "proj_out.bias"] = (c,)
 
 
+def _has_motion(cfg, where, i):
+    """the layout rule of engine.has_motion (restated: spec is importable without the engine)"""
+    if where == "mid":
+        return bool(cfg.get("motion_mid_block", False))
+    if where == "down" and cfg.get("motion_decoder_only", False):
+        return False
+    return (2 ** (i if where == "down" else 3 - i)) in tuple(cfg.get("motion_resolutions", (1, 2, 4, 8)))
+
+
 def param_shapes(cfg):
+    """state-dict names and shapes of the layout `cfg`: the motion modules a layout does not have are left out, the
+    mid-block module (mid_block.motion_modules.0.*, AnimateDiff v2) is listed where the layout has it"""
     ch = cfg["block_out_channels"]
     temb, xdim, L = ch[0] * 4, cfg["cross_attention_dim"], cfg["layers_per_block"]
     s = OrderedDict()
@@ -92,7 +103,8 @@ def param_shapes(cfg):
             _res(s, "down_blocks.%d.resnets.%d." % (i, j), cin if j == 0 else out, out, temb)
             if cfg["down_has_attn"][i]:
                 _spatial(s, "down_blocks.%d.attentions.%d." % (i, j), out, xdim)
-            _motion(s, "down_blocks.%d.motion_modules.%d." % (i, j), out)
+            if _has_motion(cfg, "down", i):
+                _motion(s, "down_blocks.%d.motion_modules.%d." % (i, j), out)
         if i < 3:
             s["down_blocks.%d.downsamplers.0.conv.weight" % i] = (out, out, 3, 3)
             s["down_blocks.%d.downsamplers.0.conv.bias" % i] = (out,)
@@ -100,6 +112,8 @@ def param_shapes(cfg):
     _res(s, "mid_block.resnets.0.", c, c, temb)
     _spatial(s, "mid_block.attentions.0.", c, xdim)
     _res(s, "mid_block.resnets.1.", c, c, temb)
+    if _has_motion(cfg, "mid", 0):     # after the resnets in the reference's module (and state-dict) order
+        _motion(s, "mid_block.motion_modules.0.", c)
     rev = list(reversed(ch))
     out = rev[0]
     for i in range(4):
@@ -111,7 +125,8 @@ def param_shapes(cfg):
             _res(s, "up_blocks.%d.resnets.%d." % (i, j), rin + skip, out, temb)
             if cfg["up_has_attn"][i]:
                 _spatial(s, "up_blocks.%d.attentions.%d." % (i, j), out, xdim)
-            _motion(s, "up_blocks.%d.motion_modules.%d." % (i, j), out)
+            if _has_motion(cfg, "up", i):
+                _motion(s, "up_blocks.%d.motion_modules.%d." % (i, j), out)
         if i < 3:
             s["up_blocks.%d.upsamplers.0.conv.weight" % i] = (out, out, 3, 3)
             s["up_blocks.%d.upsamplers.0.conv.bias" % i] = (out,)
